@@ -1,7 +1,13 @@
 """Benchmark: DCCRN-CLSKD fwd+loss step (configuration C2 of BASELINE.json) on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     (N > 1: python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N)
+
+A plain run sets up, runs W warm-up steps, times K steps and prints the result line.  --full adds
+everything else the line can carry, each in runs of its own outside the timed steps: the
+per-kernel census and the roofline of the dominant kernel, the launch count, the quality check
+against the all-fp32 step and the CPU-oracle baseline.  Both run the same steps on the same seeded
+inputs, so they compute the same outputs; --dump-outputs DIR writes the last timed step's as .npy.
 
 A step = one KnowledgeDistillation.training_step (distill.py:72-148) over B=16 synthetic 16 kHz
 4 s noisy/clean pairs per GPU: teacher + student DCCRN forwards (train-mode BN), ReviewKD
@@ -43,6 +49,36 @@ NBATCH = 4
 TRAFFIC_FILE = "r6_pmc_traffic.json"
 TRAFFIC_FILE_TRAIN = "r6_train_pmc_traffic.json"
 L = 64000
+DUMP_LIMIT = 64 << 20  # --dump-outputs: bytes written in all, at most
+SEED = 0  # torch's CPU generator: the ABF re-draw keys (clskd.distill) are drawn from it
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: every array as DIR/<name>.npy, float64 kept and everything else as float32.
+    Above DUMP_LIMIT bytes in all, an array larger than its equal share of the limit is cut down
+    to a fixed, seeded sample of its elements (flattened, in index order)."""
+    os.makedirs(dirname, exist_ok=True)
+    host = {}
+    for name, a in arrays.items():
+        if torch.is_tensor(a):  # bf16 / fp16 have no numpy form of their own
+            keep = torch.float64 if a.dtype == torch.float64 else torch.float32
+            a = a.detach().to("cpu", keep).numpy()
+        a = np.asarray(a)
+        host[name] = a if a.dtype == np.float64 else a.astype(np.float32)
+    if sum(a.nbytes for a in host.values()) > DUMP_LIMIT:
+        share = DUMP_LIMIT // len(host)
+        for name, a in host.items():
+            if a.nbytes > share:
+                idx = np.random.default_rng(SEED).choice(a.size, share // a.itemsize, replace=False)
+                host[name] = a.reshape(-1)[np.sort(idx)]
+    for name, a in host.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
+def step_outputs(parts):
+    """The tensors of a step's result dict (clskd.distill.clskd_step / SPKDDistillation): the
+    losses and the two waveforms; the nested feature lists are not outputs of the step's caller."""
+    return {k: v for k, v in parts.items() if torch.is_tensor(v)}
 
 
 def _range_push(name):
@@ -187,7 +223,7 @@ def run_c1(args, dev):
                            STUDENT_SEED).to(dev).eval()
     ps = R.to_torch_params(recipe_state_dict(cfg.dccrn_param_shapes(**cfg.STUDENT), STUDENT_SEED))
     model, total, usable = host_cpu_info()
-    legs = {}
+    legs, dumped = {}, {}
     K = max(args.steps, 10)
     for n in (16000, 8000):
         noisy, _ = synthetic_pairs(1, n, seed=5)
@@ -216,6 +252,7 @@ def run_c1(args, dev):
             torch.cuda.synchronize()
             ex.append(time.perf_counter() - t0)
         assert torch.equal(cc.out, ref_out), "executor replay differs from the eager forward"
+        dumped[f"wav_{n}"] = cc.out.clone()
         xc = torch.from_numpy(noisy)
         cpu = {}
         for threads in (usable, 1):
@@ -265,6 +302,8 @@ def run_c1(args, dev):
                                    "(the faster one is the value: a 1 s clip is too small to "
                                    "spread over many cores)"},
     }
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, dumped)
     print(json.dumps(out))
 
 
@@ -316,6 +355,8 @@ def run_c5(args, dev):
 
     fs = FusedStreamingDCCRN(student, S)
     per_hop, kern_ms = timed(fs, S)
+    if args.dump_outputs:  # the hop's output samples of every stream after the last timed hop
+        dump_outputs(args.dump_outputs, {"wav_out": fs.wav_out})
     legs["fused_all"] = dict(streams=S, ms_per_hop=round(per_hop * 1e3, 4), kernel_ms=round(kern_ms, 4),
                              frames_per_s=round(S / per_hop, 1),
                              real_time_factor=round(per_hop / (HOP / 16000.0), 5))
@@ -412,10 +453,25 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="C2 / C3 / C4: besides the timed steps, everything else the result line "
+                         "can carry, each in runs of its own: the per-kernel census steps and the "
+                         "dominant kernel's roofline (with its launches event-timed inside the "
+                         "timed steps), the launch count of a captured step, the quality check "
+                         "against the all-fp32 step and the CPU-oracle baseline.  Without it "
+                         "the fields that take such runs are null.  (--c1 / --c5 are whole legs "
+                         "of their own, CPU leg included, with or without --full.)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (losses "
+                         "and waveforms; C3: the loss and the updated flat student parameters; "
+                         "C1 / C5: the output waveforms) as DIR/<name>.npy, float32, 64 MB at most "
+                         "(rank 0's shard when N > 1).  Inputs, weights and ABF draws are seeded: "
+                         "the same arguments give the same inputs in every run")
     ap.add_argument("--cpu-steps", type=int, default=None,
-                    help="timed CPU-oracle steps (median; BASELINE.md §2: 10 for C2; C4 default 3 "
+                    help="--full: timed CPU-oracle steps (median; BASELINE.md §2: 10 for C2; C4 default 3 "
                          "timed after 1 warm-up: a bounded sample of its B=32 step)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: leave out the CPU-oracle leg")
     ap.add_argument("--abf-reinit", default="step", choices=["step", "once"])
     ap.add_argument("--launch", default=None, choices=["exec", "eager", "graph"],
                     help="default: exec for C2 (one rank), eager for C3 / C4 / multi-rank.  "
@@ -475,6 +531,7 @@ def main():
 
     from clskd import ops
     from clskd.data import synthetic_pairs
+    torch.manual_seed(SEED)  # the ABF re-draw keys: the same draws, so the same outputs, every run
     if args.c1:
         return run_c1(args, dev)
     if args.c5:
@@ -583,9 +640,9 @@ def main():
     from clskd.distill import serialized_streams
     census = None
     serial_ms = None
-    disp_us = dispatch_span_us(dev)
+    disp_us = dispatch_span_us(dev) if args.full else None
     for i in range(args.warmup):
-        last = i == args.warmup - 1 and not args.graph
+        last = i == args.warmup - 1 and not args.graph and args.full
         if last:
             torch.cuda.synchronize()
             _range_push("clskd_census")
@@ -603,7 +660,24 @@ def main():
     torch.cuda.synchronize()
     dominant = max(census.items(), key=lambda kv: kv[1][1])[0] if census else None
     census_all, dom_fn = None, None
-    if args.launch == "exec":
+    if args.launch == "exec" and not args.full:
+        # the untimed replay that --full spends on the executor census below, without its timing:
+        # a step advances the ABF re-draw counter (C3: and trains), so both modes enter the timed
+        # region with the same steps behind them and compute the same outputs
+        if hasattr(executor, "ex"):  # C2: the census replays the next capture on batch W
+            step(args.warmup)
+        else:
+            # C3 / C4: the census replays the capture alone (C3 on N > 1 ranks: fwd+loss and the
+            # backward, no all-reduce and no Adam) on the batch of the executor's last replay
+            # before the eager census step
+            from clskd.graph import StepExecutor
+            kc = max(args.warmup - 2, 0) % NBATCH
+            executor.X.copy_(Xs[kc])
+            executor.y.copy_(Ys[kc].reshape(executor.y.shape))
+            StepExecutor._replay(executor)
+            if args.train:
+                flat.bump_versions()
+    elif args.launch == "exec":
         # one more untimed step: the captured step replayed in program order on ONE stream with
         # every kernel node event-timed (clskd_exec_census) — the isolated duration of EVERY
         # kernel, library and torch alike; the dominant instance is the one with the largest
@@ -629,7 +703,7 @@ def main():
     # roctx range (rocprofv3 --marker-trace): tools/region_stats.py splits the kernel trace at it,
     # so the profile's per-kernel averages are those of exactly the timed steps
     _range_push("clskd_timed")
-    if args.launch == "eager":
+    if args.launch == "eager" and args.full:
         ops.KernelTimer.start(only=dominant)
     waited0 = getattr(executor, "throttle_s", 0.0) if executor is not None else 0.0
     t0 = time.perf_counter()
@@ -643,7 +717,9 @@ def main():
     cdist.barrier(dev)
     el = time.perf_counter() - t0
     _range_pop()
-    if args.launch == "exec":
+    if not args.full:
+        ktimes = timing = None
+    elif args.launch == "exec":
         import ctypes
         tot, cnt = ctypes.c_double(0), ctypes.c_int32(0)
         for e in getattr(executor, "ex", [executor]):
@@ -699,8 +775,18 @@ def main():
         if world > 1:
             param_hashes = [None] * world
             torch.distributed.all_gather_object(param_hashes, h)
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # what the caller of the timed path holds after its last step, copied to the host before
+        # anything below runs another step
+        if args.train:
+            dumped = dict(loss=loss, student_params=flat.data)
+        else:
+            src = executor.out if args.launch == "exec" else (graph.out if args.graph else kd.last)
+            dumped = step_outputs(src)
+        dumped = {k: v.detach().cpu() for k, v in dumped.items()}
     quality = None
-    if not args.train and not args.spkd and args.precision == "mixed":
+    if args.full and not args.train and not args.spkd and args.precision == "mixed":
         # quality gate of the metric ("SI-SNR parity ±0.01 dB"): the timed step's student
         # waveform vs the all-fp32 step on the same batch (after the timed region)
         from clskd.tools_for_loss import si_snr
@@ -729,7 +815,7 @@ def main():
                             "check is tests/test_gpu_c2_mixed.py")
 
     step_counts = None
-    if world == 1 and not args.train and not args.spkd and not args.graph:
+    if args.full and world == 1 and not args.train and not args.spkd and not args.graph:
         # after the timed region: one capture of the step, its kernel nodes counted
         step_counts = launches_per_step(kd, Xs[0], Ys[0])
     elif args.train and args.launch == "exec" and executor is not None:
@@ -740,6 +826,8 @@ def main():
 
     if rank == 0:
         frames = world * bsz * T * args.steps
+        roof = cpu = None
+    if rank == 0 and args.full:
         # dominant kernel = conv kernel instance with the largest total time
         name, (n_l, ms, flops) = max(ktimes.items(), key=lambda kv: kv[1][1])
         conv_total_ms = sum(v[1] for v in census.values())
@@ -869,6 +957,7 @@ def main():
             # GPU / CPU-oracle ratio on the same workload.  `vs_baseline` stays null: it is
             # reserved for a published number for this metric, and BASELINE.md has none
             cpu["gpu_over_cpu"] = round(frames / el / cpu["value"], 1)
+    if rank == 0:
         workload = ("C2: DCCRN-CLSKD fwd+loss (teacher 3.67M + student 0.23M params, ReviewKD "
                     "enc+dec, 14 SPKD Grams, MRSTFT)")
         if args.train:
@@ -948,6 +1037,8 @@ def main():
             "param_hash_per_rank": param_hashes,
             "cpu_baseline": cpu,
         }
+        if dumped is not None:
+            dump_outputs(args.dump_outputs, dumped)
         print(json.dumps(out))
     if world > 1:
         cdist.barrier(dev)

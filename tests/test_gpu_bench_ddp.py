@@ -57,6 +57,48 @@ def test_bench_gpus2_standalone_fwd_loss_executor():
     assert d["value"] > 0 and d["scaling"] == "weak"
 
 
+def _bench1(*extra):
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1",
+                        "--steps", "3", "--warmup", "1", *extra],
+                       cwd=REPO, capture_output=True, text=True, timeout=280)
+    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    return json.loads(lines[0])
+
+
+@pytest.mark.gpu
+@pytest.mark.timeout(600)
+def test_bench_plain_and_full_runs_write_the_same_outputs(tmp_path):
+    """A plain run times its steps and nothing else (the fields that take runs of their own are
+    null); --full fills them.  Both run the same steps on the same seeded inputs: what
+    --dump-outputs writes (float32, the losses and the student waveform of the last timed step)
+    is bitwise the same in both, and the line's loss is the dumped one."""
+    import numpy as np
+    p = _bench1("--dump-outputs", str(tmp_path / "plain"))
+    f = _bench1("--full", "--no-cpu-baseline", "--dump-outputs", str(tmp_path / "full"))
+    for d in (p, f):
+        assert d["steps"] == 3 and d["warmup"] == 1 and d["dtype"] == "bf16" and d["unit"] == "frames/s"
+        assert d["higher_is_better"] is True and d["ms_per_step"] > 0
+        frames = d["config"]["global_batch"] * d["config"]["frames_per_clip"]
+        assert abs(d["value"] * d["ms_per_step"] * 1e-3 - frames) <= 2e-3 * frames
+    for k in ("roofline", "quality", "cpu_baseline", "launches_per_step", "serialized_kernel_ms_per_step"):
+        assert p[k] is None, (k, p[k])
+    assert f["roofline"]["frac"] > 0 and f["quality"]["si_snr_delta_db"] <= 0.01
+    assert f["launches_per_step"] > 0 and f["cpu_baseline"] is None
+    names = sorted(os.listdir(tmp_path / "plain"))
+    assert names == sorted(os.listdir(tmp_path / "full")) and "student_wav.npy" in names
+    total = 0
+    for n in names:
+        a, b = np.load(tmp_path / "plain" / n), np.load(tmp_path / "full" / n)
+        assert a.dtype == np.float32 and np.isfinite(a).all(), n
+        assert a.shape == b.shape and np.array_equal(a, b), n
+        total += a.nbytes
+    assert total <= 64 << 20
+    assert np.load(tmp_path / "plain" / "student_wav.npy").shape == (16, 64000)
+    assert abs(float(np.load(tmp_path / "plain" / "loss.npy")) - p["config"]["loss"]) <= 1e-6
+
+
 @pytest.mark.gpu
 @pytest.mark.timeout(300)
 def test_rccl_communicator_and_allreduce_one_rank():

@@ -114,6 +114,38 @@ def test_bench_standalone_multi_gpu_launch_command():
     assert cmd[-4:] == ["--gpus", "8", "--steps", "5"] and cmd[-5].endswith("bench.py")
 
 
+def test_bench_dump_outputs_types_and_size_limit(tmp_path, monkeypatch):
+    """`bench.py --dump-outputs`: float64 stays, everything else is written as float32; above the
+    size limit an array larger than its share becomes the same seeded sample of its elements in
+    every run, smaller arrays are written whole, and the files stay within the limit."""
+    import importlib.util
+    import numpy as np
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(repo, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    assert bench.DUMP_LIMIT == 64 << 20
+    big = torch.arange(5000, dtype=torch.float32).reshape(50, 100)
+    arrays = dict(loss=torch.tensor(0.5, dtype=torch.float64), half=torch.ones(3, dtype=torch.bfloat16),
+                  big=big)
+    bench.dump_outputs(str(tmp_path / "a"), arrays)
+    got = {n: np.load(tmp_path / "a" / (n + ".npy")) for n in arrays}
+    assert got["loss"].dtype == np.float64 and got["loss"].shape == ()
+    assert got["half"].dtype == np.float32 and got["big"].dtype == np.float32
+    assert np.array_equal(got["big"], big.numpy())
+    monkeypatch.setattr(bench, "DUMP_LIMIT", 6000)  # a share of 2000 bytes each
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), arrays)
+    b = {n: np.load(tmp_path / "b" / (n + ".npy")) for n in arrays}
+    c = {n: np.load(tmp_path / "c" / (n + ".npy")) for n in arrays}
+    assert sum(v.nbytes for v in b.values()) <= 6000
+    assert b["big"].shape == (500,) and np.array_equal(b["big"], c["big"])
+    assert np.all(np.diff(b["big"]) > 0) and set(b["big"]) <= set(big.reshape(-1).tolist())
+    assert np.array_equal(b["half"], got["half"]) and b["loss"] == got["loss"]
+    # only the tensors of a step's result are outputs (not its nested feature lists)
+    assert set(bench.step_outputs(dict(loss=big, feats=[big], t=dict(x=big)))) == {"loss"}
+
+
 def test_pack_provenance_follows_the_current_cache_entry():
     """model.pack_provenance / pack_output (backward.tw_prebuild's source lookup): an output is
     traced to (model, group, slot) only while it is the object the registry recorded, and

@@ -19,16 +19,16 @@ for st in ${STEPS:-suite bench}; do
     tests:*)
       a=${st#tests:}; rc=0; timeout -k 10 600 $T -m gpu ${a//,/ } > $O/tests.log 2>&1 || rc=$?
       tail -2 $O/tests.log; ok $rc tests;;
-    bench) rc=0; timeout -k 10 300 python $R/bench.py $BENCH_ARGS > $O/bench.log 2>&1 || rc=$?; ok $rc bench
+    bench) rc=0; timeout -k 10 300 python $R/bench.py --full $BENCH_ARGS > $O/bench.log 2>&1 || rc=$?; ok $rc bench
       grep '^{' $O/bench.log | cut -c1-400;;
-    train) rc=0; timeout -k 10 300 python $R/bench.py --train --no-cpu-baseline > $O/bench_train.log 2>&1 || rc=$?; ok $rc train
+    train) rc=0; timeout -k 10 300 python $R/bench.py --train --full --no-cpu-baseline > $O/bench_train.log 2>&1 || rc=$?; ok $rc train
       grep '^{' $O/bench_train.log | cut -c1-300;;
-    spkd) rc=0; timeout -k 10 300 python $R/bench.py --spkd --no-cpu-baseline > $O/bench_spkd.log 2>&1 || rc=$?; ok $rc spkd;;
+    spkd) rc=0; timeout -k 10 300 python $R/bench.py --spkd --full --no-cpu-baseline > $O/bench_spkd.log 2>&1 || rc=$?; ok $rc spkd;;
     c1) rc=0; timeout -k 10 300 python $R/bench.py --c1 > $O/bench_c1.log 2>&1 || rc=$?; ok $rc c1;;
     c5) rc=0; timeout -k 10 300 python $R/bench.py --c5 > $O/bench_c5.log 2>&1 || rc=$?; ok $rc c5;;
     trace)
       ( cd /tmp && export TMPDIR=/tmp
-        rc=0; timeout -k 10 300 rocprofv3 --kernel-trace --marker-trace --stats --output-format csv -d $O/trace -o run -- python3 $R/bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline $BENCH_ARGS > $O/trace.log 2>&1 || rc=$?; ok $rc trace ) || exit $?
+        rc=0; timeout -k 10 300 rocprofv3 --kernel-trace --marker-trace --stats --output-format csv -d $O/trace -o run -- python3 $R/bench.py --gpus 1 --steps 20 --warmup 5 --full --no-cpu-baseline $BENCH_ARGS > $O/trace.log 2>&1 || rc=$?; ok $rc trace ) || exit $?
       python3 $R/tools/region_stats.py $O/trace/run 20 $O/region_stats.json > $O/region_stats.txt 2>&1 || true
       grep '^{' $O/trace.log | cut -c1-300;;
     pmc)
@@ -62,7 +62,7 @@ for st in ${STEPS:-suite bench}; do
         for c in "${CS[@]}"; do
           i=$((i+1)); rc=0
           ce=${c%%::*}; ca=""; [[ "$c" == *::* ]] && ca=${c#*::}
-          env $ce timeout -k 10 200 python $R/bench.py --no-cpu-baseline --steps 20 --warmup 5 $BENCH_ARGS $ca > $O/ab_c${i}_p$pass.log 2>&1 || rc=$?; ok $rc ab
+          env $ce timeout -k 10 200 python $R/bench.py --full --no-cpu-baseline --steps 20 --warmup 5 $BENCH_ARGS $ca > $O/ab_c${i}_p$pass.log 2>&1 || rc=$?; ok $rc ab
           echo "[$c] pass $pass: $(grep '^{' $O/ab_c${i}_p$pass.log | python3 -c 'import json,sys; d=json.loads(sys.stdin.read()); r=d["roofline"]; print(d["ms_per_step"], "ms, host", d["host_enqueue_ms_per_step"], "frac", r["frac"], r.get("kernel"), r.get("isolated_avg_launch_us"), "census", r.get("all_kernels_isolated", {}).get("ms_per_step"))')"
         done
       done;;
@@ -73,7 +73,7 @@ for st in ${STEPS:-suite bench}; do
         for c in "${CS[@]}"; do
           i=$((i+1)); rc=0
           ce=${c%%::*}; ca=""; [[ "$c" == *::* ]] && ca=${c#*::}
-          env $ce timeout -k 10 200 python $R/bench.py --no-cpu-baseline --steps 20 --warmup 5 $BENCH2_ARGS $ca > $O/ab2_c${i}_p$pass.log 2>&1 || rc=$?; ok $rc ab2
+          env $ce timeout -k 10 200 python $R/bench.py --full --no-cpu-baseline --steps 20 --warmup 5 $BENCH2_ARGS $ca > $O/ab2_c${i}_p$pass.log 2>&1 || rc=$?; ok $rc ab2
           echo "[$c] pass $pass: $(grep '^{' $O/ab2_c${i}_p$pass.log | python3 -c 'import json,sys; d=json.loads(sys.stdin.read()); r=d["roofline"]; print(d["ms_per_step"], "ms, host", d["host_enqueue_ms_per_step"], "frac", r["frac"], r.get("kernel"), r.get("isolated_avg_launch_us"), "census", r.get("all_kernels_isolated", {}).get("ms_per_step"))')"
         done
       done;;
@@ -81,12 +81,12 @@ for st in ${STEPS:-suite bench}; do
       head -3 $O/hostprof.txt;;
     trace_train_exec)
       ( cd /tmp && export TMPDIR=/tmp
-        rc=0; timeout -k 10 400 rocprofv3 --kernel-trace --marker-trace --stats --output-format csv -d $O/tetrace -o run -- python3 $R/bench.py --train --launch exec --steps 10 --warmup 3 --no-cpu-baseline > $O/tetrace.log 2>&1 || rc=$?; ok $rc trace_train_exec ) || exit $?
+        rc=0; timeout -k 10 400 rocprofv3 --kernel-trace --marker-trace --stats --output-format csv -d $O/tetrace -o run -- python3 $R/bench.py --train --launch exec --steps 10 --warmup 3 --full --no-cpu-baseline > $O/tetrace.log 2>&1 || rc=$?; ok $rc trace_train_exec ) || exit $?
       python3 $R/tools/region_stats.py $O/tetrace/run 10 $O/train_exec_region_stats.json > $O/train_exec_region_stats.txt 2>&1 || true
       grep '^{' $O/tetrace.log | cut -c1-300;;
     trace_train)
       ( cd /tmp && export TMPDIR=/tmp
-        rc=0; timeout -k 10 400 rocprofv3 --kernel-trace --marker-trace --stats --output-format csv -d $O/ttrace -o run -- python3 $R/bench.py --train --steps 10 --warmup 3 --no-cpu-baseline > $O/ttrace.log 2>&1 || rc=$?; ok $rc trace_train ) || exit $?
+        rc=0; timeout -k 10 400 rocprofv3 --kernel-trace --marker-trace --stats --output-format csv -d $O/ttrace -o run -- python3 $R/bench.py --train --steps 10 --warmup 3 --full --no-cpu-baseline > $O/ttrace.log 2>&1 || rc=$?; ok $rc trace_train ) || exit $?
       python3 $R/tools/region_stats.py $O/ttrace/run 10 $O/train_region_stats.json > $O/train_region_stats.txt 2>&1 || true
       grep '^{' $O/ttrace.log | cut -c1-300;;
     py:*) f=${st#py:}; f=${f//,/ }; rc=0; timeout -k 10 300 python $R/$f > $O/py_$(basename ${f%% *} .py).txt 2>&1 || rc=$?

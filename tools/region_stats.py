@@ -2,8 +2,10 @@
 (`clskd_census`: the census step on one stream; `clskd_timed`: exactly the K timed steps).
 
     rocprofv3 --kernel-trace --marker-trace --stats --output-format csv -d D -o run -- \
-        python3 bench.py --steps K --warmup W --no-cpu-baseline
+        python3 bench.py --steps K --warmup W --full --no-cpu-baseline
     python tools/region_stats.py D/run K out.json
+
+(--full: a plain bench run has no census step, only the `clskd_timed` range.)
 
 The ranges are host-side push/pop pairs, each bracketed by a device synchronisation in bench.py,
 so every kernel of the region starts and ends inside it.  Reports, per region: kernel launches,

@@ -16,9 +16,9 @@ mkdir -p $O
 )
 python3 $R/tools/pmc_traffic.py $O/fetch/run_counter_collection.csv $O/write/run_counter_collection.csv $R/profiles/r3_pmc_traffic.json > $O/traffic.txt
 cp $R/profiles/r3_pmc_traffic.json $O/r3_pmc_traffic.json
-timeout -k 10 300 python $R/bench.py > $O/bench.log 2>&1
-timeout -k 10 200 python $R/bench.py --train --no-cpu-baseline > $O/bench_train.log 2>&1
-timeout -k 10 200 python $R/bench.py --spkd --no-cpu-baseline > $O/bench_spkd.log 2>&1
+timeout -k 10 300 python $R/bench.py --full > $O/bench.log 2>&1
+timeout -k 10 200 python $R/bench.py --train --full --no-cpu-baseline > $O/bench_train.log 2>&1
+timeout -k 10 200 python $R/bench.py --spkd --full --no-cpu-baseline > $O/bench_spkd.log 2>&1
 timeout -k 10 200 python $R/bench.py --c1 > $O/bench_c1.log 2>&1
 timeout -k 10 300 python $R/bench.py --c5 > $O/bench_c5.log 2>&1
 cd /tmp && export TMPDIR=/tmp
