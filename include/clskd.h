@@ -796,6 +796,59 @@ int clskd_stream_hop(const clskd_stream_hop_args* a, void* stream);
  * projection, decoders 0-5, mask, iSTFT, end, then per encoder layer (staged, conv done) — n <= 40
  * values (after a synchronize). */
 int clskd_stream_hop_marks(int64_t* out, int32_t n);
+/* ------------------------------------------------------------------------------------------
+ * Streaming hop of asteroid's DCCRNet_mini ('DCCRN-CL-test', the model the reference distils and
+ * evaluates): one 6.25 ms hop of its eval-mode forward for B streams as ONE launch (one workgroup
+ * per stream).
+ * Replaces: the per-hop launch sequence of clskd.streaming.StreamingDCCRNet_mini — STFTFB analysis
+ * row (no centring, Nyquist bin dropped), six complex encoder blocks that look one frame AHEAD
+ * each (5x2 kernel, no time padding, no bias; re / im BatchNorm and PReLU), two complex LSTM layers
+ * with carried state (nn.LSTM gates i, f, g, o; rr - ii, ri + ir), complex Linear with bias, five
+ * causal transposed-conv blocks and the output layer (with bias) over skips cat([x, enc_out]),
+ * BoundComplexMask('tanh') times the spectrum (Nyquist 0), STFTFB synthesis row and the plain
+ * overlap-add (oracle/asteroid_cpu.py:85-138 with train=False).
+ * Weights are fp32 copies of the packed operands in k-quad layout [K/4][N][4] as for
+ * clskd_stream_hop: encoder K order (kf*2+kt, ci) with encoder 0's two input channels padded to
+ * four; transposed convs per parity (tap, [input (re, im) | skip (re, im)] channels); LSTM input
+ * [K][8H] of both modules ([re-module 4H | im-module 4H], bias_ih + bias_hh folded into lstm_b);
+ * W_hh as [H][2*4H]; the Linear as [2H][2P] (K = (re H | im H), n = half*P + c*D4 + f, P = D4*C6/2);
+ * analysis filters [400][514]; synthesis filters [516][400].  BatchNorm as eval [scale | shift]
+ * over the (re | im) channels + the two PReLU slopes (re, im).
+ * `state` holds per-stream rings with the layout of clskd_stream_hop_args (zero at the start of a
+ * stream): xwin 400; spectrum [7][514]; encoder output i [7-i][128>>i][enc_cout[i]]; Linear output
+ * [2][D4][C6]; transposed-conv output d [2][2*(D4<<d)][dec_co[d]]; h, c [2 layers][2 modules]
+ * [2 halves][H]; synthesis frames [4][400].
+ * Hop t (0, 1, ..) consumes x_in[b][100] (live = 1, drain = 0) or nothing (live = 0, drain = k >= 1:
+ * the k-th hop after the last input hop) and writes wav_out[b][100]: block t - 9 of the offline
+ * output (frame u = t - 3 is the newest complete one, the mask lags it by 6 frames).  Frames the
+ * offline forward does not have are zeros: everything before its frame 0, and in drain hop k the
+ * spectrum, the encoders, the LSTM / Linear and transposed conv d's output for k > d + 1. */
+typedef struct {
+  const float* stft_w;       /* [100][514][4] */
+  const float* istft_w;      /* [129][400][4] */
+  const float* enc_w[6];
+  const float* enc_coef[6];  /* [2*Co] scale | shift */
+  const float* enc_alpha[6]; /* [2] re, im */
+  const float* lstm_w[2];    /* [K/4][8H][4] */
+  const float* lstm_b[2];    /* [8H] */
+  const float* lstm_whh[2];  /* [H/4][8H][4] */
+  const float* lin_w;        /* [2H/4][2P][4] */
+  const float* lin_b;        /* [2P] */
+  const float* dec_w[6][2];  /* per parity */
+  const float* dec_b[6][2];  /* NULL for d < 5 (no bias) */
+  const float* dec_coef[6];  /* d < 5 */
+  const float* dec_alpha[6]; /* d < 5: [2] re, im */
+  float* state;
+  int64_t state_stride;
+  const float* x_in;         /* [B][100] */
+  float* wav_out;            /* [B][100] */
+  int32_t B, t, live, drain;
+  int32_t H, D4;
+  int32_t enc_cin[6], enc_cout[6];
+  int32_t dec_ca[6], dec_cb[6], dec_co[6];
+  int32_t off_xwin, off_spec, off_enc[6], off_decin, off_dout[5], off_h, off_c, off_frames;
+} clskd_stream_hop_mini_args;
+int clskd_stream_hop_mini(const clskd_stream_hop_mini_args* a, void* stream);
 /* Diagnostic (-DCLSKD_EXPERIMENTS builds only; else an error): wall-clock (100 MHz) timeline of
  * workgroup 0 of the last halo-tiled fp32 conv launched with CLSKD_H32_DEBUG_MODE=5 — waves 0
  * and 4 (one SIMD) at [0, 64) and [64, 128): after each chunk barrier, after each chunk's MFMAs,

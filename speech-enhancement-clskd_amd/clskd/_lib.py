@@ -98,6 +98,23 @@ class StreamHopArgs(C.Structure):
                 ("off_frames", C.c_int32)]
 
 
+class StreamHopMiniArgs(C.Structure):
+    """clskd_stream_hop_mini_args (include/clskd.h): the fused DCCRNet_mini hop."""
+    _fields_ = [("stft_w", C.c_void_p), ("istft_w", C.c_void_p), ("enc_w", C.c_void_p * 6),
+                ("enc_coef", C.c_void_p * 6), ("enc_alpha", C.c_void_p * 6),
+                ("lstm_w", C.c_void_p * 2), ("lstm_b", C.c_void_p * 2), ("lstm_whh", C.c_void_p * 2),
+                ("lin_w", C.c_void_p), ("lin_b", C.c_void_p), ("dec_w", (C.c_void_p * 2) * 6),
+                ("dec_b", (C.c_void_p * 2) * 6), ("dec_coef", C.c_void_p * 6),
+                ("dec_alpha", C.c_void_p * 6), ("state", C.c_void_p), ("state_stride", C.c_int64),
+                ("x_in", C.c_void_p), ("wav_out", C.c_void_p), ("B", C.c_int32), ("t", C.c_int32),
+                ("live", C.c_int32), ("drain", C.c_int32), ("H", C.c_int32), ("D4", C.c_int32),
+                ("enc_cin", C.c_int32 * 6), ("enc_cout", C.c_int32 * 6), ("dec_ca", C.c_int32 * 6),
+                ("dec_cb", C.c_int32 * 6), ("dec_co", C.c_int32 * 6), ("off_xwin", C.c_int32),
+                ("off_spec", C.c_int32), ("off_enc", C.c_int32 * 6), ("off_decin", C.c_int32),
+                ("off_dout", C.c_int32 * 5), ("off_h", C.c_int32), ("off_c", C.c_int32),
+                ("off_frames", C.c_int32)]
+
+
 assert C.sizeof(KtabEntry) == 8
 assert C.sizeof(DrawJob) == 48
 assert C.sizeof(GramJob) == 88
@@ -222,6 +239,7 @@ SIGNATURES = {
     "clskd_exec_marks": (_i32, [_p, _i32]),
     "clskd_exec_marks_read": (_i32, [_p, C.POINTER(C.c_float), _i32]),
     "clskd_stream_hop": (_i32, [C.POINTER(StreamHopArgs), _p]),
+    "clskd_stream_hop_mini": (_i32, [C.POINTER(StreamHopMiniArgs), _p]),
     "clskd_stream_hop_marks": (_i32, [C.POINTER(C.c_int64), _i32]),
     "clskd_h32_marks": (_i32, [C.POINTER(C.c_int64), _i32]),
     "clskd_spkd_bn_bwd": (_i32, [_p, _i32, _i64, _i64, _i32, _i32, _p, _p, _p, _p, _p, _f32, _p, _p,

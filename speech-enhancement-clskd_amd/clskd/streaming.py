@@ -375,3 +375,405 @@ class FusedStreamingDCCRN(StreamingDCCRN):
         self._hop()
         self.steps_run += 1
         return self.wav_out.clone() if self.t - 1 - LOOKAHEAD >= 3 else None
+
+
+# ======================================================================================
+# asteroid DCCRNet_mini ('DCCRN-CL-test', clskd.asteroid): the distilled student the reference
+# checkpoints and evaluates, hop by hop
+# ======================================================================================
+MINI_LOOKAHEAD = 6                    # the six encoder blocks read one frame ahead each
+MINI_LATENCY_HOPS = MINI_LOOKAHEAD + 3  # + the 3 hops that complete an uncentred 400-sample frame
+MINI_MIN_SAMPLES = (MINI_LATENCY_HOPS + 1) * HOP
+
+
+class _StreamingMini:
+    """step() / finish() / process() / reset() of the two DCCRNet_mini streaming engines.
+
+    Time structure (oracle/asteroid_cpu.py:85-138, eval-mode BatchNorm).  Hop h brings samples
+    [100h, 100h + 100); frame u covers [100u, 100u + 400) (no centring), so it is complete after
+    hop u + 3.  Encoder block i reads its input at frames t and t + 1 and therefore emits frame
+    u - (i + 1) when frame u arrives; the LSTMs (carried state), the Linear, the five transposed
+    convs and the output layer are causal and emit frame u - 6; the mask of frame u - 6 times
+    spectrum frame u - 6 enters a 4-frame plain overlap-add that completes output block u - 6.
+    Input hop h yields output block h - 9: 9 hops = 56.25 ms of algorithmic latency.
+
+    Frames the offline forward does not have are zeros wherever a later layer reads them
+    (BatchNorm + PReLU of a zero row is not zero, and the output layer has a bias): every frame
+    before frame 0, and after the last input hop (T frames in all) the spectrum, the encoders and
+    the LSTM / Linear at once, transposed conv d (0..5) from drain hop d + 2 on.
+
+    Equal to ``model.eval()(x)``: running statistics.  A train-mode forward (what the reference's
+    eval.py runs) normalises with the statistics of the whole utterance and cannot be streamed.
+    Weights are packed once at construction: re-create the object after the parameters change."""
+
+    def __init__(self, model, batch):
+        if model.training:
+            raise ValueError(f"{type(self).__name__} runs eval-mode BatchNorm (running statistics): "
+                             "call model.eval() first")
+        self.m = model
+        self.B = int(batch)
+        self.dev = next(model.parameters()).device
+        mk = model.masker
+        self.encs = list(mk.encoders[:-1])
+        self.decs = [(blk.deconv, blk) for blk in list(mk.decoders)[1:]] + [(mk.output_layer[0], None)]
+        self.rnn = mk.encoders[-1].rnn
+        if len(self.encs) != 6 or len(self.decs) != 6 or len(self.rnn.rnns) != 2:
+            raise NotImplementedError("built for the 6-block, 2-LSTM DCCRNet_mini")
+        self.H = self.rnn.rnns[0].re_module.rnn.hidden_size
+        self.Cin = [2 * e.conv.re_module.in_channels for e in self.encs]    # (re | im) channels
+        self.Cenc = [2 * e.conv.re_module.out_channels for e in self.encs]
+        self.Fenc = [128 >> i for i in range(6)]                             # encoder output bins
+        self.D4, self.C6 = self.Fenc[5], self.Cenc[5]
+        self.Fd = [self.D4 << d for d in range(6)]                           # transposed-conv input bins
+        self.Co = [2 * dc.re_module.out_channels for dc, _ in self.decs]
+        self.Ca = [self.C6] + self.Co[:-1]
+        self.t = 0
+        self.steps_run = 0
+
+    # ---- eval-mode BatchNorm of the (re | im) channels as [scale | shift], the two PReLU slopes
+    def _bn_coef(self, blk):
+        nr, ni = blk.norm.re_module, blk.norm.im_module
+        with torch.no_grad():
+            g, b, rm, rv = (torch.cat([getattr(nr, k), getattr(ni, k)]).float().contiguous()
+                            for k in ("weight", "bias", "running_mean", "running_var"))
+            x = torch.empty(1, g.numel(), device=self.dev)
+            coef = ops.batch_norm_bftc(x, None, g, b, rm, rv, False, nr.momentum, nr.eps)
+            alpha = torch.cat([blk.activation.re_module.weight,
+                               blk.activation.im_module.weight]).float().contiguous()
+        return coef, alpha
+
+    def _zero_state(self):
+        raise NotImplementedError
+
+    def _hop(self, live, drain):
+        raise NotImplementedError
+
+    def reset(self):
+        """Back to the start of a stream: zero state, hop counter 0 (one object, clip after clip)."""
+        self._zero_state()
+        self.t = 0
+
+    def _check_hop(self, x_hop):
+        if tuple(x_hop.shape) != (self.B, HOP):
+            raise ValueError(f"expected a hop of shape ({self.B}, {HOP}), got {tuple(x_hop.shape)}")
+
+    def step(self, x_hop):
+        """Feed 100 new samples per stream; returns the enhanced block 9 hops behind (None for the
+        first 9 hops)."""
+        self._check_hop(x_hop)
+        self.x_in.copy_(x_hop)
+        self._hop(True, 0)
+        self.steps_run += 1
+        return self.wav_out.clone() if self.t > MINI_LATENCY_HOPS else None
+
+    def finish(self):
+        """End of the stream: the 9 drain hops -> [B][900], the last 9 blocks of the clip (6 hops
+        empty the transposed convs, 3 flush the overlap-add).  reset() starts the next clip."""
+        if self.t < MINI_LATENCY_HOPS + 1:
+            raise ValueError(f"a clip needs at least {MINI_MIN_SAMPLES} samples (7 frames: one for "
+                             f"the last encoder), got {self.t * HOP}")
+        outs = []
+        for k in range(1, MINI_LATENCY_HOPS + 1):
+            self._hop(False, k)
+            outs.append(self.wav_out.clone())
+        return torch.cat(outs, 1)
+
+    def process(self, x):
+        """Whole clip x [B][L] -> [B][L], equal to the offline eval-mode forward: the complete
+        hops, the drain, zeros for the L % 100 samples the offline model pads (pad_x_to_y)."""
+        if x.dim() != 2 or x.shape[0] != self.B:
+            raise ValueError(f"expected [{self.B}][L] input, got {tuple(x.shape)}")
+        L = x.shape[1]
+        if L < MINI_MIN_SAMPLES:
+            raise ValueError(f"a clip needs at least {MINI_MIN_SAMPLES} samples (7 frames: one for "
+                             f"the last encoder), got {L}")
+        self.reset()
+        outs = []
+        for h in range(L // HOP):
+            y = self.step(x[:, h * HOP:(h + 1) * HOP])
+            if y is not None:
+                outs.append(y)
+        outs.append(self.finish())
+        if L % HOP:
+            outs.append(torch.zeros(self.B, L % HOP, device=x.device, dtype=torch.float32))
+        return torch.cat(outs, 1)
+
+
+class StreamingDCCRNet_mini(_StreamingMini):
+    """DCCRNet_mini hop by hop with the library's per-layer kernels (about 60 launches per hop),
+    the steady-state hop captured once as a hipGraph and replayed (graph=True): the second,
+    independent implementation the fused hop is checked against.  See _StreamingMini for the
+    contract and the time structure.  Buffers are time-major windows [slot][B][F][C], oldest
+    slot first, shifted by one slot per hop."""
+
+    CAPTURE_AFTER = MINI_LATENCY_HOPS + 2  # eager hops first: every launch plan of a full hop exists
+
+    def __init__(self, model, batch, graph=True):
+        super().__init__(model, batch)
+        m, B, H, D4, C6 = self.m, self.B, self.H, self.D4, self.C6
+        f32 = dict(device=self.dev, dtype=torch.float32)
+        z = lambda *shape: torch.zeros(*shape, **f32)  # noqa: E731
+        self.x_in, self.wav_out = z(B, HOP), z(B, HOP)
+        self.xwin, self.xtmp = z(B, WIN), z(B, WIN - HOP)
+        self.spec = z(MINI_LOOKAHEAD + 1, B, 514)          # spectrum frames u-6 .. u
+        self.spec_b = z(B, 256, 1, 2)
+        Fin = [256 >> i for i in range(6)]
+        self.ewin = [z(2, B, Fin[i], self.Cin[i]) for i in range(6)]       # encoder i input: u-i-1, u-i
+        self.eraw = [z(B, self.Fenc[i], 1, self.Cenc[i]) for i in range(6)]
+        # encoder i output ring: frames u-7 .. u-i-1 (slots 0, 1 = the skip of transposed conv 5-i)
+        self.ering = [z(7 - i, B, self.Fenc[i], self.Cenc[i]) for i in range(6)]
+        self.gx = z(2, B, 8 * H)
+        self.h, self.c = z(2, 2, 2 * B, H), z(2, 2, 2 * B, H)
+        self.hs = z(2, 2 * B, H)
+        self.rio = [(z(B, H), z(B, H)) for _ in range(2)]
+        self.dwin = [z(2, B, self.Fd[d], self.Ca[d]) for d in range(6)]    # transposed conv d input: u-7, u-6
+        self.draw = [z(B, 2 * self.Fd[d], 1, self.Co[d]) for d in range(5)]
+        self.mask = z(B, 256, 1, 2)
+        self.est = z(B, 1, 516)
+        self.frames, self.ftmp = z(B, 4, WIN), z(B, 3, WIN)               # synthesis frames u-9 .. u-6
+        self._state = ([self.x_in, self.wav_out, self.xwin, self.spec, self.h, self.c, self.mask,
+                        self.frames] + self.ewin + self.ering + self.dwin)
+        self.tmp = {}
+        # ---- operands, packed once
+        with torch.no_grad():
+            self.w_fb = m._fb_w()
+            self.w_enc = [m._enc_w(i) for i in range(6)]
+            self.w_lstm = [m._lstm_w(li) for li in range(2)]
+            self.w_lin = m._lin_w()
+            self.w_dec = [[m._dec_w(dc, parity, self.Ca[d] // 2) for parity in (0, 1)]
+                          for d, (dc, _) in enumerate(self.decs)]
+        self.ebn = [self._bn_coef(e) for e in self.encs]
+        self.dbn = [self._bn_coef(blk) for _, blk in self.decs[:-1]]
+        self.graph = None
+        self._scope = None
+        self.use_graph = graph
+        self.replays = 0
+
+    def _zero_state(self):
+        for t in self._state:
+            t.zero_()
+
+    _shift = StreamingDCCRN._shift
+
+    def _bn_apply(self, x, y, bn):
+        coef, alpha = bn
+        Cn = x.shape[-1]
+        sc = coef.data_ptr()
+        ops.check(ops.lib().clskd_bn_apply_reim(x.data_ptr(), y.data_ptr(), x.numel() // Cn, Cn, sc,
+                                                sc + 4 * Cn, alpha.data_ptr(), ops._dt(x),
+                                                ops._stream()), "bn_apply_reim")
+
+    def _body(self, u, live, drain):
+        """One hop whose newest frame is u (drain: the drain hop 1.., else 0)."""
+        from .asteroid import DCCRNet_mini
+        B, H, D4, C6 = self.B, self.H, self.D4, self.C6
+        Ch = C6 // 2
+        # ---- shift every window / ring by one frame
+        self.xtmp.copy_(self.xwin[:, HOP:])
+        self.xwin[:, :WIN - HOP].copy_(self.xtmp)
+        if live:
+            self.xwin[:, WIN - HOP:].copy_(self.x_in)
+        else:
+            self.xwin[:, WIN - HOP:].zero_()
+        for w in [self.spec] + self.ewin + self.ering + self.dwin:
+            self._shift(w)
+        self.ftmp.copy_(self.frames[:, 1:])
+        self.frames[:, :3].copy_(self.ftmp)
+        # ---- STFTFB analysis of the newest window; Nyquist bin dropped (asteroid.py:301-305)
+        if live and u >= 0:
+            ops.conv([Seg(self.xwin, 0, SegGeom(HOP, WIN, 0, HOP, 1, 4))],
+                     [(0, kt) for kt in range(4)], B, 1, 1, 514, self.w_fb[0], None, self.spec[-1],
+                     OutMap(514, 0, 514))
+            ops.spec_bftc(self.spec[-1].view(B, 1, 514), 0, 257, 256, self.spec_b)
+            self.ewin[0][1].copy_(self.spec_b.view(B, 256, 2))
+        else:
+            self.spec[-1].zero_()
+            self.ewin[0][1].zero_()
+        # ---- encoders: block i emits frame u-i-1 from its input's frames (u-i-1, u-i)
+        for i in range(6):
+            Fo, Co = self.Fenc[i], self.Cenc[i]
+            dsts = [self.ering[i][-1]] + ([self.ewin[i + 1][1]] if i < 5 else [])
+            if live and u >= i + 1:
+                ops.conv([_seg_tm(self.ewin[i])], [(kf - 2, kt) for kf in range(5) for kt in range(2)],
+                         B, Fo, 1, Co, self.w_enc[i], None, self.eraw[i], OutMap(Fo * Co, Co, Co),
+                         stride_f=2)
+                self._bn_apply(self.eraw[i].view(B, Fo, Co), dsts[0], self.ebn[i])
+                for dst in dsts[1:]:
+                    dst.copy_(dsts[0])
+            else:
+                for dst in dsts:
+                    dst.zero_()
+        # ---- complex LSTMs on frame u-6 (carried state), complex Linear -> transposed conv 0 input
+        if live and u >= MINI_LOOKAHEAD:
+            r_in = None
+            for li in range(2):
+                wp, bias, whh = self.w_lstm[li]
+                for half in range(2):
+                    if li == 0:
+                        segs = [_seg_tm(self.ering[5], 1, 1, half * Ch, Ch)]
+                        taps = [(f, 0) for f in range(D4)]
+                    else:
+                        segs, taps = [Seg(r_in[half], 0, SegGeom(H, H, 0, H, 1, 1))], [(0, 0)]
+                    ops.conv(segs, taps, B, 1, 1, 8 * H, wp, bias, self.gx[half], OutMap(8 * H, 0, 8 * H))
+                ops.lstm_cell(self.gx, 4 * H, 8 * H, whh, 2, 2 * B, H, self.h[li], self.c[li],
+                              2 * B * H, H, self.hs, 2 * B * H, H)
+                ro, io = self.rio[li]
+                ops.complex_combine(self.hs[0, :B], self.hs[1, B:], self.hs[0, B:], self.hs[1, :B], ro, io)
+                r_in = (ro, io)
+            wre, bre, wim, bim = self.w_lin
+            segs = [Seg(r_in[h], 0, SegGeom(H, H, 0, H, 1, 1)) for h in range(2)]
+            for half, (w, b) in enumerate(((wre, bre), (wim, bim))):
+                ops.conv(segs, [(0, 0)], B, 1, 1, Ch * D4, w, b, self.dwin[0][1],
+                         OutMap(D4 * C6, 0, 0, 1, C6, D4), out_offset=half * Ch)
+        else:
+            self.dwin[0][1].zero_()
+        # ---- transposed convs (the output layer last): frame u-6 from frames (u-7, u-6)
+        for d in range(6):
+            F, Co = self.Fd[d], self.Co[d]
+            last = d == 5
+            dst = self.mask if last else self.dwin[d + 1][1]
+            if not (u >= MINI_LOOKAHEAD and drain <= d + 1):
+                dst.zero_()
+                continue
+            segs = [_seg_tm(self.dwin[d], 0, 2), _seg_tm(self.ering[5 - d], 0, 2)]
+            raw = self.mask if last else self.draw[d]
+            for parity in (0, 1):
+                taps = [(dF, 1 - kt) for _, dF in DCCRNet_mini._DEC_TAPS[parity] for kt in (0, 1)]
+                wp, bias = self.w_dec[d][parity]
+                ops.conv(segs, taps, B, F, 1, Co, wp, bias, raw,
+                         OutMap(2 * F * Co, Co, Co, of_mul=2, of_add=parity))
+            if not last:
+                self._bn_apply(self.draw[d].view(B, 2 * F, Co), dst, self.dbn[d])
+        # ---- bounded mask times spectrum frame u-6, synthesis row, plain overlap-add
+        ops.check(ops.lib().clskd_mask_bdt(self.spec[0].data_ptr(), 514, self.mask.data_ptr(), 1, B, 1,
+                                           self.est.data_ptr(), 516, ops._stream()), "mask_bdt")
+        ops.conv([Seg(self.est, 0, SegGeom(516, 516, 0, 516, 1, 1))], [(0, 0)], B, 1, 1, WIN,
+                 self.w_fb[1], None, self.frames, OutMap(4 * WIN, 0, 0), out_offset=3 * WIN)
+        ops.ola_hop(self.frames, None, HOP, HOP, WIN - HOP, False, self.wav_out)
+
+    def _capture(self):
+        """Capture the steady-state hop (every frame exists) inside a CaptureScope, so the graph
+        owns the stream-K workspaces of its conv launches."""
+        torch.cuda.synchronize(self.dev)
+        s = ops.capture_stream(self.dev)
+        g = torch.cuda.CUDAGraph()
+        self._scope = ops.CaptureScope([s])
+        try:
+            with torch.cuda.graph(g, stream=s, capture_error_mode="thread_local"), torch.no_grad():
+                self._body(MINI_LOOKAHEAD, True, 0)  # recorded, not run: the state does not advance
+        finally:
+            self._scope.end()
+        self.graph = g
+
+    def _hop(self, live, drain):
+        u = self.t - 3
+        steady = live and u >= MINI_LOOKAHEAD
+        if steady and self.use_graph and self.graph is None and self.steps_run >= self.CAPTURE_AFTER:
+            self._capture()
+        if steady and self.graph is not None:
+            self.graph.replay()
+            self.replays += 1
+        else:
+            with torch.no_grad():
+                self._body(u, live, drain)
+        self.t += 1
+
+
+class FusedStreamingDCCRNet_mini(_StreamingMini):
+    """DCCRNet_mini hop by hop as ONE launch per hop (clskd_stream_hop_mini,
+    csrc/stream_hop_mini.hip): one workgroup per stream walks the analysis row, the encoders, the
+    complex LSTMs, the Linear, the transposed convs, the bounded mask, the synthesis row and the
+    overlap-add with each layer's current frame in LDS and the older frames in per-stream rings.
+    Same step() / finish() / process() / reset() contract and latency (9 hops) as
+    StreamingDCCRNet_mini.  Weights are fp32 copies in the kernel's k-quad layout [K/4][N][4],
+    built once: re-create the object after changing the model's parameters."""
+
+    def __init__(self, model, batch):
+        super().__init__(model, batch)
+        from . import _lib
+        m, B, dev, H, D4, C6 = self.m, self.B, self.dev, self.H, self.D4, self.C6
+        f32 = dict(device=dev, dtype=torch.float32)
+        self.x_in, self.wav_out = torch.zeros(B, HOP, **f32), torch.zeros(B, HOP, **f32)
+        keep = []
+
+        def q4(w, K, ci=None):
+            """packed [N][Kp] (first K columns real) -> k-quad [K/4][N][4]; ci: pad each tap's ci
+            input channels to a quad (encoder 0's (re, im))."""
+            w = w.float()[:, :K]
+            N = w.shape[0]
+            if ci is not None:
+                w = torch.nn.functional.pad(w.reshape(N, K // ci, ci), (0, 4 - ci)).reshape(N, -1)
+                K = w.shape[1]
+            assert K % 4 == 0, K
+            t = w.reshape(N, K // 4, 4).permute(1, 0, 2).contiguous()
+            keep.append(t)
+            return t.data_ptr()
+
+        def p(t):
+            t = t.detach().float().contiguous()
+            keep.append(t)
+            return t.data_ptr()
+
+        a = _lib.StreamHopMiniArgs()
+        with torch.no_grad():
+            wa, ws = m._fb_w()
+            a.stft_w, a.istft_w = q4(wa, WIN), q4(ws, 516)
+            for i, e in enumerate(self.encs):
+                a.enc_w[i] = q4(m._enc_w(i), 10 * self.Cin[i], ci=2 if i == 0 else None)
+                coef, alpha = self._bn_coef(e)
+                a.enc_coef[i], a.enc_alpha[i] = p(coef), p(alpha)
+                a.enc_cin[i], a.enc_cout[i] = self.Cin[i], self.Cenc[i]
+            for li in range(2):
+                wp, bias, whh = m._lstm_w(li)
+                K = D4 * (C6 // 2) if li == 0 else H
+                a.lstm_w[li], a.lstm_b[li] = q4(wp, K), p(bias)
+                a.lstm_whh[li] = q4(whh.float().reshape(8 * H, H), H)
+            wre, bre, wim, bim = m._lin_w()
+            a.lin_w = q4(torch.cat([wre[:, :2 * H], wim[:, :2 * H]], 0), 2 * H)
+            a.lin_b = p(torch.cat([bre, bim]))
+            for d, (dc, blk) in enumerate(self.decs):
+                Cb = self.Cenc[5 - d]
+                for parity in (0, 1):
+                    wp, bias = m._dec_w(dc, parity, self.Ca[d] // 2)
+                    a.dec_w[d][parity] = q4(wp, (6 if parity == 0 else 4) * (self.Ca[d] + Cb))
+                    a.dec_b[d][parity] = p(bias) if bias is not None else None
+                if blk is not None:
+                    coef, alpha = self._bn_coef(blk)
+                    a.dec_coef[d], a.dec_alpha[d] = p(coef), p(alpha)
+                a.dec_ca[d], a.dec_cb[d], a.dec_co[d] = self.Ca[d], Cb, self.Co[d]
+        a.H, a.D4, a.B = H, D4, B
+        # per-stream state layout (floats)
+        off = 0
+
+        def take(n):
+            nonlocal off
+            o = off
+            off += (n + 3) // 4 * 4
+            return o
+
+        a.off_xwin = take(WIN)
+        a.off_spec = take(7 * 514)
+        for i in range(6):
+            a.off_enc[i] = take((7 - i) * self.Fenc[i] * self.Cenc[i])
+        a.off_decin = take(2 * D4 * C6)
+        for d in range(5):
+            a.off_dout[d] = take(2 * 2 * self.Fd[d] * self.Co[d])
+        a.off_h = take(2 * 4 * H)
+        a.off_c = take(2 * 4 * H)
+        a.off_frames = take(4 * WIN)
+        a.state_stride = off
+        self.fstate = torch.zeros(B, off, **f32)
+        a.state = self.fstate.data_ptr()
+        a.x_in, a.wav_out = self.x_in.data_ptr(), self.wav_out.data_ptr()
+        self._args, self._keep = a, keep
+
+    def _zero_state(self):
+        self.fstate.zero_()
+        self.x_in.zero_()
+        self.wav_out.zero_()
+
+    def _hop(self, live, drain):
+        a = self._args
+        a.t, a.live, a.drain = self.t, int(live), int(drain)
+        ops.check(ops.lib().clskd_stream_hop_mini(a, ops._stream()), "stream_hop_mini")
+        self.t += 1
