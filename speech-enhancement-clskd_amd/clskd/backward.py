@@ -335,6 +335,9 @@ def dccrn_backward(m, tape, enc, dec, dec_in, lstm_io, g, pg, acc_params=False, 
     dev = tape["spec"].device
     kn = m.kernel_num
     nl = len(kn) - 1
+    # split-product (bf16 hi / lo planes) data gradients: the same gate as the iSTFT / MRSTFT
+    # framing GEMMs below — only a student whose compute mode is 'f32x3' leaves the exact engine
+    planes = getattr(m, "compute", "fp32") == "f32x3"
 
     # ---------------- ConviSTFT + clamp + mask 'E' (DCCRN.py:207-237)
     dmask = None
@@ -402,8 +405,9 @@ def dccrn_backward(m, tape, enc, dec, dec_in, lstm_io, g, pg, acc_params=False, 
         dseg = Seg(draw, 0, dgeom)
         taps_b = [(p - 2 * dF, kt) for p in (0, 1) for _, dF in DCCRN._DEC_TAPS[p] for kt in (0, 1)]
         # planes where a destination is wider than 32 channels (the bf16 engine's 32-wide tile
-        # loses to the exact engine: profiles/r6_planes_micro.txt)
-        pl = _planes_of(draw, dgeom) if max(Cof, Csk) >= _PLANES_MIN_N else None
+        # loses to the exact engine: profiles/r6_planes_micro.txt) — of an 'f32x3' student only:
+        # an fp32 student's data gradients stay on the exact engine (set_precision's contract)
+        pl = _planes_of(draw, dgeom) if (planes and max(Cof, Csk) >= _PLANES_MIN_N) else None
         for s0, Cs, dst, t0, Tt in ((0, Cof, g["dec_in"] if d == 0 else g["dec"][d - 1], out_t0,
                                      out_t.shape[2]),
                                     (Cof, Csk, g["enc"][nl - 1 - d], 0, T)):
@@ -544,7 +548,7 @@ def dccrn_backward(m, tape, enc, dec, dec_in, lstm_io, g, pg, acc_params=False, 
             continue
         dgeom = SegGeom(Co, Fo * T * Co, T * Co, Co, Fo, T)
         dseg = Seg(draw, 0, dgeom)
-        pl = _planes_of(draw, dgeom) if Ci >= _PLANES_MIN_N else None
+        pl = _planes_of(draw, dgeom) if (planes and Ci >= _PLANES_MIN_N) else None
         for p in (0, 1):
             kfs = [kf for kf in range(5) if kf % 2 == p]
             taps_b = [((p - kf + 2) // 2, 1 - kt) for kf in kfs for kt in range(2)]

@@ -49,8 +49,13 @@ _STUDENT_SPLIT = os.environ.get("CLSKD_STUDENT_SPLIT", "1") == "1"
 # the training step of a 'mixed' student (C3): bit 0 — weight gradients on split products
 # (csrc/wgrad_x3.hip, the default: 20.2 -> 19.0 ms per step); bit 1 — the taped forward's and the
 # backward's data-gradient fp32 convs too (measured +0.2 ms on top: the split engine displaces
-# the halo / pointwise kernels of the narrow layers); bit 2 — the taped forward only (the
-# data gradients stay exact).  CLSKD_TRAIN_SPLIT=0: the whole training step exact (A/B,
+# the halo / pointwise kernels of the narrow layers); bit 2 — the taped forward only.
+# Whatever these bits say, the wide (>= 33-channel) encoder / decoder data gradients and the
+# iSTFT / MRSTFT framing data gradients of a 'mixed' (compute 'f32x3') student run on bf16
+# hi / lo split products while CLSKD_DGRAD_PLANES=1 (the default, backward.py): that switch, not
+# train_split, decides whether a mixed student's data gradients are exact.  A student whose
+# compute mode is 'fp32' (precision='fp32', the C4 SPKD student) never takes those paths.
+# CLSKD_TRAIN_SPLIT=0 with CLSKD_DGRAD_PLANES=0: the whole training step exact (A/B,
 # profiles/r5_train_split_ab.txt)
 # default 5 = weight gradients + the taped forward (round 6: 14.93-15.04 -> 14.74-14.87 ms,
 # profiles/r6_train_split_ab.txt); 1 = weight gradients only

@@ -387,7 +387,8 @@ def test_backward_refuses_redrawn_abf_weights():
 def test_clskd_backward_mixed_precision_close_to_fp32():
     """precision='mixed' (teacher + ReviewKD activations in bf16, the bench default): the
     student's gradients stay close to the all-fp32 step's (the ReviewKD backward reads bf16
-    saved activations; gradients themselves are fp32 unless CLSKD_RKD_GRAD_BF16=1)."""
+    saved activations and, with the default CLSKD_RKD_GRAD_BF16=1, stores its mid-channel
+    gradient maps bf16 too; CLSKD_RKD_GRAD_BF16=0 keeps those maps fp32)."""
     from clskd.data import synthetic_pairs
     noisy, clean = synthetic_pairs(2, 8000, seed=23)
     X, y = torch.from_numpy(noisy).to(DEV), torch.from_numpy(clean).to(DEV)
@@ -406,6 +407,49 @@ def test_clskd_backward_mixed_precision_close_to_fp32():
     worst.sort(reverse=True)
     print(worst[:5])
     assert worst[0][0] < 5e-2, worst[:5]
+
+
+def _backward_bits(kd, X, y, planes, monkeypatch):
+    """Every student parameter gradient and tap gradient of one backward, with the split-plane
+    data-gradient switch forced to `planes`."""
+    import clskd.backward as bw
+    monkeypatch.setattr(bw, "_DGRAD_PLANES", planes)
+    grads = {p: torch.empty_like(p) for p in kd.student.parameters()}
+    out = kd.forward_with_tape(X, y)
+    from clskd import ops
+    ts = getattr(kd.student, "train_split", 0)
+    with ops.split_products(bool(ts & 2), wgrad=bool(ts & 1)):
+        g = bw.clskd_backward(out, kd.student, kd.review_encoder, kd.review_decoder, grads)
+    torch.cuda.synchronize()
+    res = {n: grads[p].clone() for n, p in kd.student.named_parameters()}
+    res["tap/wav"] = g["wav"].clone()
+    res["tap/dec_in"] = g["dec_in"].clone()
+    for k in ("enc", "dec"):
+        for i, t in enumerate(g[k]):
+            res[f"tap/{k}{i}"] = t.clone()
+    return res
+
+
+def test_fp32_student_data_gradients_ignore_the_planes_switch(monkeypatch):
+    """set_precision('fp32') promises every GEMM on exact-f32 MFMA: the bf16 hi / lo split-plane
+    data gradients (CLSKD_DGRAD_PLANES, on by default) belong to the 'f32x3' student of
+    precision='mixed' only.  An fp32 student's backward is bitwise the same with the switch on
+    and off — every parameter and every tap gradient — while the mixed student's changes, so its
+    fast path is still taken."""
+    from clskd.data import synthetic_pairs
+    noisy, clean = synthetic_pairs(2, 8000, seed=25)
+    X, y = torch.from_numpy(noisy).to(DEV), torch.from_numpy(clean).to(DEV)
+    kd = _kd("fp32")
+    assert kd.student.compute == "fp32"
+    on = _backward_bits(kd, X, y, True, monkeypatch)
+    off = _backward_bits(kd, X, y, False, monkeypatch)
+    diff = [n for n in on if not torch.equal(on[n], off[n])]
+    assert not diff, f"fp32 student gradients depend on the planes switch: {diff[:8]}"
+    kd = _kd("mixed")
+    assert kd.student.compute == "f32x3"
+    on = _backward_bits(kd, X, y, True, monkeypatch)
+    off = _backward_bits(kd, X, y, False, monkeypatch)
+    assert any(not torch.equal(on[n], off[n]) for n, _ in kd.student.named_parameters())
 
 
 def test_reviewkd_backward_bf16_gradient_storage():
