@@ -190,6 +190,28 @@ int32_t clskd_conv_fold_capable(const clskd_conv_desc* d);
 #define CLSKD_WLAYOUT_DIRECT 1
 
 int clskd_conv2d_fwd(const clskd_conv_desc* d, void* stream);
+
+/* Plan of the halo-tiled split-product kernel (conv_halo_split3_kernel) for a descriptor, computed
+ * on the host without launching anything (no device needed): launches = 0 when the descriptor is
+ * not taken (it runs on conv_split3_kernel), else 1; col_halves = 2 when even / odd workgroups of
+ * that launch own output columns [0, 32) / [32, N) (the weight planes of all columns do not fit).  seg_min_off /
+ * seg_max_off: the smallest and largest element offset from seg[s].ptr that any staging load of
+ * any tile touches (walked with the kernel's index arithmetic; min > max: segment never read).
+ * Pointers of the descriptor are only checked for alignment, never dereferenced. */
+typedef struct {
+  int32_t launches, col_halves;
+  int32_t cw;               /* channels per chunk (8 | 16) */
+  int32_t tile_f, tile_t;   /* output tile: F-rows x time steps (8 x 32 | 4 x 64) */
+  int32_t nfb, ntb, ntiles; /* tile grid */
+  int32_t halo_f, halo_t;   /* halo extent in pixels */
+  int32_t nchunk, nstep;    /* channel chunks per tile; 16-deep MFMA steps per chunk */
+  int32_t grid;             /* workgroups */
+  int32_t reserved_;
+  int64_t lds_bytes;        /* dynamic LDS of a workgroup */
+  int64_t seg_min_off[CLSKD_MAX_SEGS];
+  int64_t seg_max_off[CLSKD_MAX_SEGS];
+} clskd_halo_split_info;
+int clskd_conv_halo_split_plan(const clskd_conv_desc* d, clskd_halo_split_info* info);
 /* Instance name ("kernel<template args>", as rocprofv3 reports it) of the kernel the calling
  * thread's last successful clskd_conv2d_fwd launched — the dispatch policy (direct / halo /
  * 128- or 256-row bf16 engine / fp32 engine) is the library's, so hosts label timings with it. */

@@ -46,6 +46,16 @@ class ConvDesc(C.Structure):
                 ("bn_fold", C.c_void_p)]
 
 
+class HaloSplitInfo(C.Structure):
+    """clskd_halo_split_info (include/clskd.h): host-side plan of conv_halo_split3_kernel."""
+    _fields_ = [("launches", C.c_int32), ("col_halves", C.c_int32), ("cw", C.c_int32), ("tile_f", C.c_int32),
+                ("tile_t", C.c_int32), ("nfb", C.c_int32), ("ntb", C.c_int32),
+                ("ntiles", C.c_int32), ("halo_f", C.c_int32), ("halo_t", C.c_int32),
+                ("nchunk", C.c_int32), ("nstep", C.c_int32), ("grid", C.c_int32), ("reserved_", C.c_int32),
+                ("lds_bytes", C.c_int64), ("seg_min_off", C.c_int64 * MAX_SEGS),
+                ("seg_max_off", C.c_int64 * MAX_SEGS)]
+
+
 BN_FOLD_REPL = 8
 
 
@@ -146,6 +156,7 @@ SIGNATURES = {
     "clskd_experiments_build": (_i32, []),
     "clskd_conv2d_fwd": (_i32, [C.POINTER(ConvDesc), _p]),
     "clskd_conv_fold_capable": (_i32, [C.POINTER(ConvDesc)]),
+    "clskd_conv_halo_split_plan": (_i32, [C.POINTER(ConvDesc), C.POINTER(HaloSplitInfo)]),
     "clskd_bn_fold_state_size": (_i64, [_i32]),
     "clskd_abf_bn1_fold": (_i32, [_p, _i32, _i32, _i32, _i64, _i64, _i64, _i32, _p, _p, _i32, _p]),
     "clskd_conv_direct_np": (_i32, [_i32]),

@@ -337,6 +337,7 @@ int launch_conv_direct(const clskd_conv_desc& d, hipStream_t st);
 int launch_conv_pointwise(const clskd_conv_desc& d, hipStream_t st, bool* launched);
 int launch_conv_halo_f32(const clskd_conv_desc& d, hipStream_t st, bool* launched);
 int launch_conv_split3(const clskd_conv_desc& d, hipStream_t st, bool* launched, bool force);
+int launch_conv_halo_split(const clskd_conv_desc& d, hipStream_t st, bool* launched);
 
 }  // namespace clskd
 
@@ -351,6 +352,7 @@ bool conv_halow_takes(const clskd_conv_desc& d);
 #endif
 bool conv_pointwise_takes(const clskd_conv_desc& d);
 bool conv_split3_takes(const clskd_conv_desc& d, bool force);
+bool conv_halo_split_takes(const clskd_conv_desc& d);
 }  // namespace clskd
 
 // The kernel a descriptor dispatches to folds the BatchNorm finalize (clskd_bn_fold): the
@@ -368,6 +370,7 @@ static bool fold_capable(const clskd_conv_desc& dd) {
   clskd_conv_desc d = dd;  // the fp32 engines see CLSKD_F32 (F32X3 only asks for the split)
   d.compute = CLSKD_F32;
   if (conv_pointwise_takes(d)) return false;
+  if (split && conv_halo_split_takes(d)) return true;
   if (conv_split3_takes(d, split)) return true;
   return knob(KNOB_NO_HALO32) != 1 && conv_halo_f32_takes(d);
 }
@@ -462,6 +465,18 @@ extern "C" int clskd_conv2d_fwd(const clskd_conv_desc* dp, void* stream) {
     if (rc != CLSKD_OK) return rc;
     if (launched) {
       CLSKD_LAUNCH_CHECK("conv2d_pointwise");
+      return CLSKD_OK;
+    }
+  }
+  // split products asked for per descriptor (CLSKD_F32X3: the student of precision 'mixed'):
+  // the halo-tiled kernel first (CLSKD_HALO_SPLIT=1).  The global A/B knob CLSKD_F32_SPLIT=1 keeps
+  // routing plain fp32 descriptors to conv_split3_kernel alone.
+  if (want_split) {
+    bool launched = false;
+    const int rc = launch_conv_halo_split(d, st, &launched);
+    if (rc != CLSKD_OK) return rc;
+    if (launched) {
+      CLSKD_LAUNCH_CHECK("conv2d_halo_split");
       return CLSKD_OK;
     }
   }

@@ -3,6 +3,12 @@ T=643): encoder 5x2 stride-(2,1) layers, a decoder polyphase parity-0 layer and 
 Times `iters` back-to-back launches with HIP events.  Diagnostic only.
 
     python tools/conv_micro.py [--iters 50] [--only enc4,dec1]
+
+--student: the student's fp32 split-product launches instead (CLSKD_F32X3, B=16, T=643), each on
+conv_split3_kernel and on conv_halo_split3_kernel (CLSKD_HALO_SPLIT=0 / 1) interleaved in this one
+process; per route the minimum and the spread of --rounds repetitions of --iters launches.
+
+    python tools/conv_micro.py --student --iters 20 --rounds 3 [--only enc3,dec2p0]
 """
 import argparse
 import os
@@ -88,14 +94,89 @@ def ab(a, dev, names):
               flush=True)
 
 
+# the student's fp32 split-product launches of the C2 step: (segment channels, N, kind, F_in)
+STUDENT = {
+    "enc2": ((16,), 32, "enc", 64), "enc3": ((32,), 64, "enc", 32), "enc4": ((64,), 64, "enc", 16),
+    "enc5": ((64,), 64, "enc", 8),
+    "dec0p0": ((64, 64), 64, "dec0", 4), "dec0p1": ((64, 64), 64, "dec1", 4),
+    "dec1p0": ((64, 64), 64, "dec0", 8), "dec1p1": ((64, 64), 64, "dec1", 8),
+    "dec2p0": ((64, 64), 32, "dec0", 16), "dec2p1": ((64, 64), 32, "dec1", 16),
+    "dec3p0": ((32, 32), 16, "dec0", 32), "dec3p1": ((32, 32), 16, "dec1", 32),
+    "dec4p0": ((16, 16), 8, "dec0", 64),
+}
+
+
+def make_student(segc, co, kind, fi, dev):
+    g = torch.Generator(device="cpu").manual_seed(0)
+    segs = [ops.seg_bftc((torch.randn(B, fi, T, c, generator=g) * 0.5).to(dev)) for c in segc]
+    if kind == "enc":
+        taps = [(kf - 2, kt - 1) for kf in range(5) for kt in range(2)]
+        Fo, sf, mul, add = fi // 2, 2, 1, 0
+    else:
+        par = int(kind[-1])
+        taps = [(dF, -kt) for dF in ((1, 0, -1), (1, 0))[par] for kt in (0, 1)]
+        Fo, sf, mul, add = fi, 1, 2, par
+    K = len(taps) * sum(segc)
+    wp = ops.pack_weight((torch.randn(co, len(taps), sum(segc), generator=g) * 0.05).to(dev), K)
+    bias = torch.zeros(co, device=dev)
+    out = torch.zeros(B, Fo * mul, T, co, device=dev)
+    omap = ops.OutMap(Fo * mul * T * co, T * co, co, of_mul=mul, of_add=add)
+    st = torch.empty(ops.conv_mblocks(B, Fo, T) * co * 2, device=dev, dtype=torch.float64)
+
+    def run():
+        with ops.split_products(True):
+            ops.conv(segs, taps, B, Fo, T, co, wp, bias, out, omap, stride_f=sf, stats=st,
+                     mfma_only=True)
+    return run, (B * Fo * T, co, K)
+
+
+def student(a, dev, names):
+    """conv_split3_kernel (CLSKD_HALO_SPLIT=0) against conv_halo_split3_kernel (1) on the student's
+    split-product launches: the two routes interleaved in this one process, `rounds` repetitions of
+    `iters` back-to-back launches each; minimum and spread (max - min) of the repetitions."""
+    from clskd import _lib
+    try:
+        default = _lib.set_knob("CLSKD_HALO_SPLIT", 1)
+        routes = (0, 1)
+    except Exception:  # a library without the halo-tiled split kernel: the old route alone
+        routes = (0,)
+    for name in names:
+        run, (M, N, K) = make_student(*STUDENT[name], dev=dev)
+        res = {v: [] for v in routes}
+        kn = {}
+        for r in range(a.rounds):
+            for v in routes:
+                if len(routes) > 1:
+                    _lib.set_knob("CLSKD_HALO_SPLIT", v)
+                for _ in range(2):
+                    run()
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for _ in range(a.iters):
+                    run()
+                e1.record()
+                torch.cuda.synchronize()
+                res[v].append(e0.elapsed_time(e1) * 1e3 / a.iters)
+                kn[v] = ops.conv_kernel_of_last_launch()
+        line = "  ".join(f"{'halo_split' if v else 'split3'} min {min(t):6.1f} spread {max(t) - min(t):4.1f} us "
+                         f"[{kn[v]}]" for v, t in res.items())
+        print(f"{name:7s} M={M:7d} N={N:3d} K={K:4d}  {line}", flush=True)
+    if len(routes) > 1:
+        _lib.set_knob("CLSKD_HALO_SPLIT", default)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--student", action="store_true",
+                    help="the student's split-product launches: split3 against halo_split")
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--only", default="")
     ap.add_argument("--ab", default="", help="KNOB=v1,v2: interleaved A/B of a dispatch knob")
     ap.add_argument("--rounds", type=int, default=5)
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
+    if a.student:
+        return student(a, dev, [n for n in STUDENT if not a.only or n in a.only.split(",")])
     names = [n for n in CFGS if not a.only or n in a.only.split(",")]
     if a.ab:
         return ab(a, dev, names)
