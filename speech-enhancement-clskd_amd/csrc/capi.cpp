@@ -85,6 +85,15 @@ static void init_knobs() {
   }
 }
 
+int device_cu_count() {
+  static const int ncu = [] {
+    int v = 256;
+    (void)hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, 0);
+    return v > 0 ? v : 256;
+  }();
+  return ncu;
+}
+
 int knob(KnobId k) {
   std::call_once(g_knob_once, init_knobs);
   return g_knob[k].load(std::memory_order_relaxed);

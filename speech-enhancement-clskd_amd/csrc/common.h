@@ -80,12 +80,48 @@ inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s);
 
 inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
+// compute units of device 0, read once (capi.cpp); 256 when there is no device to ask
+int device_cu_count();
+
 // ---- device helpers ---------------------------------------------------------------------
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 // 4 channels of fp32 / bf16 storage <-> f32x4 (8- or 16-B accesses)
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
+typedef short s16x4 __attribute__((ext_vector_type(4)));
+
+// hi / lo bf16 split of 4 fp32 values (RNE both): the operands of the 3 x bf16 split products
+__device__ __forceinline__ void split4(const f32x4 v, s16x4& hi, s16x4& lo) {
+  bf16x4 h, l;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    h[i] = (__bf16)v[i];
+    l[i] = (__bf16)(v[i] - (float)h[i]);
+  }
+  hi = __builtin_bit_cast(s16x4, h);
+  lo = __builtin_bit_cast(s16x4, l);
+}
+
+// One 1-KiB LDS-DMA wave instruction: lane l copies 16 B from gsrc to lds_base + 16*l.  Inline
+// asm (cdna_hip_programming.md §5.7): hipcc neither tracks nor waits for it, so a kernel's counted
+// vmcnt waits are the only synchronisation.  M0 is set and restored inside.
+__device__ __forceinline__ void glds16(const void* gsrc, unsigned lds_base) {
+  unsigned keep;
+  asm volatile(
+      "s_mov_b32 %0, m0\n\t"
+      "s_mov_b32 m0, %2\n\t"
+      "s_nop 0\n\t"
+      "global_load_lds_dwordx4 %1, off\n\t"
+      "s_mov_b32 m0, %0"
+      : "=&s"(keep)
+      : "v"(gsrc), "s"(lds_base)
+      : "memory");
+}
+
+__device__ __forceinline__ unsigned lds_addr(const void* p) {
+  return (unsigned)(uintptr_t)(const __attribute__((address_space(3))) char*)p;
+}
 
 template <typename T>
 __device__ __forceinline__ f32x4 load4(const T* p);

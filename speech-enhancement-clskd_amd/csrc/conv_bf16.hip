@@ -51,25 +51,6 @@ __device__ __forceinline__ void store_out<__bf16>(__bf16* p, float v) { *p = (__
 
 __host__ __device__ constexpr int stage_bytes(int BM, int BK, int BN) { return (BM + BN) * BK * 2; }
 
-// One 1-KiB LDS-DMA wave instruction: lane l copies 16 B from gsrc to lds_base + 16*l.
-// Inline asm (cdna_hip_programming.md §5.7): hipcc neither tracks nor waits for it, so the
-// pipeline's counted vmcnt waits are the only synchronisation.  M0 is set and restored inside.
-__device__ __forceinline__ void glds16(const void* gsrc, unsigned lds_base) {
-  unsigned keep;
-  asm volatile(
-      "s_mov_b32 %0, m0\n\t"
-      "s_mov_b32 m0, %2\n\t"
-      "s_nop 0\n\t"
-      "global_load_lds_dwordx4 %1, off\n\t"
-      "s_mov_b32 m0, %0"
-      : "=&s"(keep)
-      : "v"(gsrc), "s"(lds_base)
-      : "memory");
-}
-
-__device__ __forceinline__ unsigned lds_addr(const void* p) {
-  return (unsigned)(uintptr_t)(const __attribute__((address_space(3))) char*)p;
-}
 }  // namespace v2
 
 struct ConvArgsV2 {
@@ -538,11 +519,7 @@ int launch_conv_bf16(const clskd_conv_desc& d, hipStream_t st) {
     // worth of work) but halve the workgroup count: pick them unless the tail rounds eat the
     // gain — a 256-row tile costs ~1.6 rounds-equivalents of a 128-row tile, one workgroup per
     // CU either way.
-    static const int ncu = [] {
-      int v = 256;
-      (void)hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, 0);
-      return v > 0 ? v : 256;
-    }();
+    const int ncu = device_cu_count();
     const int64_t M = (int64_t)d.B * d.Fo * d.To;
     const int64_t ny = cdiv(d.N, d.N <= 64 ? 64 : d.N <= 128 ? 128 : 256);
     const int64_t r256 = cdiv(cdiv(M, 256) * ny, ncu), r128 = cdiv(cdiv(M, 128) * ny, ncu);

@@ -43,22 +43,6 @@ namespace g8 {
 
 __device__ __attribute__((aligned(64))) unsigned char zero_page[64];
 
-// One 1-KiB LDS-DMA wave instruction: lane l copies 16 B from gsrc to lds_base + 16*l.  Inline
-// asm (cdna_hip_programming.md §5.7): hipcc neither tracks nor waits for it, so the counted
-// vmcnt waits below are the only synchronisation.
-__device__ __forceinline__ void glds16(const void* gsrc, unsigned lds_base) {
-  unsigned keep;
-  asm volatile(
-      "s_mov_b32 %0, m0\n\t"
-      "s_mov_b32 m0, %2\n\t"
-      "s_nop 0\n\t"
-      "global_load_lds_dwordx4 %1, off\n\t"
-      "s_mov_b32 m0, %0"
-      : "=&s"(keep)
-      : "v"(gsrc), "s"(lds_base)
-      : "memory");
-}
-
 // Tap-addressed pieces (TA): the buffer form of the LDS-DMA, four 1-KiB pieces per call.  Lane l
 // copies 16 B from rsrc.base + voff[l] to m0 + 16*l (out-of-range offsets, >= num_records = 2^31,
 // read as zeros: masked taps and N-tail weight rows cost no address arithmetic).  Piece p lands at
@@ -114,10 +98,6 @@ __device__ __forceinline__ void bdma2(unsigned v0, unsigned v1, i32x4 rs, unsign
       : "=&s"(keep)
       : "s"(lds_base), "s"(rs), "v"(v0), "v"(v1), "n"(O0), "n"(O0 + OS)
       : "memory");
-}
-
-__device__ __forceinline__ unsigned lds_addr(const void* p) {
-  return (unsigned)(uintptr_t)(const __attribute__((address_space(3))) char*)p;
 }
 
 template <typename T>
@@ -1001,11 +981,7 @@ static int launch_g8(const clskd_conv_desc& d, hipStream_t st) {
     (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     attr_set = true;
   }
-  static const int ncu = [] {
-    int v = 256;
-    (void)hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, 0);
-    return v > 0 ? v : 256;
-  }();
+  const int ncu = device_cu_count();
   const int64_t M = (int64_t)d.B * d.Fo * d.To;
   const int64_t n_mt = cdiv(M, BM), n_nt = cdiv(d.N, BN);
   const int64_t ntiles = n_mt * n_nt;

@@ -21,11 +21,11 @@
 //   * the epilogue issues a static number of stores (invalid rows to a sink page) and BatchNorm
 //     statistics accumulate per workgroup in fp64 (same partial-slot contract as the engines).
 // N = 64 layers whose [64][K] weights do not fit beside the halo buffers run as two 32-column
-// launches (the input halo is staged twice; cheap at fp32 MFMA rates).
+// launches (the input halo is staged twice; cheap at fp32 MFMA rates).  The tile walk, the chunk
+// table, the DMA slot word and the statistics reduction are conv_halo_common.h's.
 #include <stdlib.h>
 
-#include "bnfold.h"
-#include "common.h"
+#include "conv_halo_common.h"
 
 namespace clskd {
 
@@ -42,58 +42,22 @@ constexpr int TT = 32;     // output time steps per tile
 constexpr int NW = 8;      // waves
 constexpr int CW = 8;      // fp32 channels per chunk: 32-B pixel rows (two 16-B halves)
 constexpr int MAXG = 4;    // max LDS-DMA wave-instructions per wave per chunk (32 KiB halo buffer)
-constexpr int MAXCH = 64;  // max chunks (ctot <= 512)
-
-__device__ __forceinline__ void glds16(const void* gsrc, unsigned lds_base) {
-  unsigned keep;
-  asm volatile(
-      "s_mov_b32 %0, m0\n\t"
-      "s_mov_b32 m0, %2\n\t"
-      "s_nop 0\n\t"
-      "global_load_lds_dwordx4 %1, off\n\t"
-      "s_mov_b32 m0, %0"
-      : "=&s"(keep)
-      : "v"(gsrc), "s"(lds_base)
-      : "memory");
-}
-
-__device__ __forceinline__ unsigned lds_addr(const void* p) {
-  return (unsigned)(uintptr_t)(const __attribute__((address_space(3))) char*)p;
-}
+constexpr int MAXCH = HALO_MAXCH;  // max chunks (ctot <= 512)
 
 // 16-B half of pixel p's 32-B row that holds channel group j: conflict-free fragment reads
 // (16 consecutive pixels of one half cover all 64 banks)
 __device__ __forceinline__ int swz(int p) { return (p >> 3) & 1; }
-
-// loop constants laundered through a VGPR into an SGPR: never re-loaded from the kernarg
-// segment inside the loop (scalar loads would share lgkmcnt with the fragment reads)
-__device__ __forceinline__ int sconst(int v) {
-  asm volatile("" : "+v"(v));
-  return __builtin_amdgcn_readfirstlane(v);
-}
-__device__ __forceinline__ int64_t vconst64(int64_t v) {
-  asm volatile("" : "+v"(v));
-  return v;
-}
 }  // namespace h32
 
 struct Halo32Args {
   clskd_conv_desc d;
-  int32_t nchunk;
-  int32_t chunk_seg[h32::MAXCH];
-  int32_t chunk_c0[h32::MAXCH];    // channel offset inside the segment
-  int32_t chunk_kofs[h32::MAXCH];  // channel offset of the chunk inside one tap's ctot channels
-  int32_t dfmin, dtmin;            // halo origin relative to (fo*stride_f, to)
-  int32_t HF, HT, NPIX;            // halo extent (pixels) and count
+  HaloGeom g;
   int32_t NGH;                     // DMA wave-instructions per wave per chunk
   int32_t halo_bytes;              // bytes per halo buffer (NW * NGH KiB)
   int32_t k4;                      // k-quads of resident weights (ntaps * ctot / 4)
-  int32_t nfb, ntb, ntiles;        // tile grid: F-blocks, T-blocks, total
-  int32_t nblk128;                 // statistics slots (ceil(M/128))
   int32_t tap_pix[16];             // halo pixel offset of tap t for output (0, 0)
   int32_t tap_kq[16];              // k-quad offset of tap t (t * ctot / 4)
   BnFoldArgs f;                    // folded BatchNorm finalize (f.acc != nullptr)
-  int32_t stats_ld;                // channels per statistics slot row
 };
 
 // DBG (timing-only, experiments build): 1 no halo DMA, 2 fragments read once per chunk instead
@@ -103,6 +67,7 @@ template <int NB, int NTAPS, int DBG = 0>
 __global__ __launch_bounds__(512) void conv_halo_f32_kernel(const Halo32Args a) {
   using namespace h32;
   const clskd_conv_desc& d = a.d;
+  const HaloGeom& g = a.g;
   constexpr int NBW = NB * 32;        // resident weight columns (zero beyond N)
   // accumulator chains per column block: 2 MFMA chains per wave (64-cycle dependent latency =
   // the issue interval, so alternating two accumulators never stalls)
@@ -143,91 +108,55 @@ __global__ __launch_bounds__(512) void conv_halo_f32_kernel(const Halo32Args a) 
       }
     }
   }
-  if (tid < a.nchunk) {
-    const int sg = a.chunk_seg[tid];
-    const clskd_seg& S = d.seg[sg];
-    const uint64_t base = (uint64_t)(uintptr_t)(S.ptr + a.chunk_c0[tid]);
-    ctA[tid] = make_int4((int)(unsigned)base, (int)(unsigned)(base >> 32), (int)S.sF, (int)S.sT);
-    ctB[tid] = make_int4((int)S.sB, S.F, S.T, a.chunk_kofs[tid]);
-  }
+  halo_ctab_fill(ctA, ctB, d, g, 4);
   if (tid < 16) ttab[tid] = a.tap_pix[tid] | (a.tap_kq[tid] << 16);
-  if (d.stats) {
-    for (int64_t s = (int64_t)blockIdx.x + gridDim.x; s < a.nblk128; s += gridDim.x)
-      for (int i = tid; i < d.N * 2; i += 512) d.stats[s * a.stats_ld * 2 + i] = 0.0;
-  }
+  if (d.stats) halo_stats_zero_unowned(d.stats, d.N, g.stats_ld, g.nblk128);
   float bcol[NB];
   int64_t coff[NB];
-#pragma unroll
-  for (int nb = 0; nb < NB; ++nb) {
-    const int n = nb * 32 + l32;
-    bcol[nb] = (d.bias && n < d.N) ? d.bias[n] : 0.f;
-    coff[nb] = vconst64(n < d.N ? (int64_t)(n / d.nlo) * d.oNhi + (int64_t)(n % d.nlo) * d.oNlo : -1);
-  }
-  const int nchunk = sconst(a.nchunk), ntb = sconst(a.ntb), nfb = sconst(a.nfb);
+  halo_bias_coff<NB, true>(d, 0, d.N, l32, bcol, coff);
+  const int nchunk = sconst(g.nchunk), ntb = sconst(g.ntb), nfb = sconst(g.nfb);
   const int NGH = sconst(a.NGH);
   const int Fo = sconst(d.Fo), To = sconst(d.To), sfr = sconst(d.stride_f);
-  const int dfmin = sconst(a.dfmin), dtmin = sconst(a.dtmin);
+  const int dfmin = sconst(g.dfmin), dtmin = sconst(g.dtmin);
   const int64_t oB = vconst64(d.oB), oF = vconst64(d.oF), oT = vconst64(d.oT);
   const int of_mul = sconst(d.of_mul), of_add = sconst(d.of_add);
   // global address space: a laundered generic pointer would make the stores FLAT, which count
   // on lgkmcnt too — every fragment wait in the loop would then degrade to lgkmcnt(0)
   gfloat* const outp = reinterpret_cast<gfloat*>(vconst64((int64_t)(uintptr_t)d.out));
-  // per-lane DMA slot geometry, packed: hf | ht << 8 | source half << 16 | valid << 20
+  // per-lane DMA slots (2 per pixel; sub = the swizzled source half)
   int dmg[MAXG];
   {
-    const int HT = a.HT, NPIX = a.NPIX;
+    const int HT = g.HT, NPIX = g.NPIX;
 #pragma unroll
     for (int i = 0; i < MAXG; ++i) {
       const int slot = (wave * NGH + i) * 64 + lane;
       const int p = slot >> 1;
-      const bool ok = i < NGH && p < NPIX;
-      const int pp = ok ? p : 0;
-      const int hf = pp / HT, ht = pp - (pp / HT) * HT;
-      dmg[i] = hf | (ht << 8) | (((slot & 1) ^ swz(p)) << 16) | ((ok ? 1 : 0) << 20);
+      dmg[i] = halo_slot_pack(p, (slot & 1) ^ swz(p), i < NGH && p < NPIX, HT);
     }
   }
-  const int prow0 = wave * sfr * sconst(a.HT) + l32;  // halo pixel of (F-row wave, time l32)
+  const int prow0 = wave * sfr * sconst(g.HT) + l32;  // halo pixel of (F-row wave, time l32)
   __syncthreads();
   if constexpr (DBG == 9) return;  // prologue only
 
   const uint64_t zero_addr = (uint64_t)(uintptr_t)g_h32_zero;
   const unsigned hlds0 = __builtin_amdgcn_readfirstlane(lds_addr(hbuf));
-  const int per = (sconst(a.ntiles) + gridDim.x - 1) / gridDim.x;
+  const int per = (sconst(g.ntiles) + gridDim.x - 1) / gridDim.x;
   const int tile_begin = blockIdx.x * per;
-  const int ntile_blk = max(0, min(sconst(a.ntiles), tile_begin + per) - tile_begin);
+  const int ntile_blk = max(0, min(sconst(g.ntiles), tile_begin + per) - tile_begin);
 
-  struct Cur { int b, fb, tb; };
-  auto cur_of = [&](int tile) {
-    Cur c;
-    c.tb = tile % ntb;
-    const int r = tile / ntb;
-    c.fb = r % nfb;
-    c.b = r / nfb;
-    return c;
-  };
-  auto advance = [&](Cur& c) {
-    if (++c.tb == ntb) {
-      c.tb = 0;
-      if (++c.fb == nfb) { c.fb = 0; ++c.b; }
-    }
-  };
-
-  auto issue = [&](const Cur& c, int ch, int buf) {
+  auto issue = [&](const HaloCursor& c, int ch, int buf) {
     if constexpr (DBG == 1 || DBG == 8) return;
-    const int4 ea = ctA[ch];
-    const int4 eb = ctB[ch];
-    const float* base = reinterpret_cast<const float*>(((uint64_t)(unsigned)ea.y << 32) | (unsigned)ea.x) +
-                        (int64_t)c.b * eb.x;
+    const HaloChunk<float> k = halo_chunk<float>(ctA, ctB, ch);
+    const float* base = k.base + (int64_t)c.b * k.sB;
     const int fi_lo = c.fb * FT * sfr + dfmin, ti_lo = c.tb * TT + dtmin;
     const unsigned dst = hlds0 + buf * halo_bytes;
 #pragma unroll
     for (int i = 0; i < MAXG; ++i) {
       if (i < NGH) {
-        const int g = dmg[i];
-        const int fi = fi_lo + (g & 0xff), ti = ti_lo + ((g >> 8) & 0xff);
-        const bool ok = ((g >> 20) & 1) && (unsigned)fi < (unsigned)eb.y && (unsigned)ti < (unsigned)eb.z;
-        const uint64_t src = ok ? (uint64_t)(uintptr_t)(base + (int64_t)fi * ea.z + (int64_t)ti * ea.w +
-                                                        ((g >> 16) & 1) * 4)
+        bool ok;
+        const HaloSlotSrc s = halo_slot_src(dmg[i], fi_lo, ti_lo, k.F, k.T, ok);
+        const uint64_t src = ok ? (uint64_t)(uintptr_t)(base + (int64_t)s.fi * k.sF + (int64_t)s.ti * k.sT +
+                                                        s.sub * 4)
                                 : zero_addr;
         glds16((const void*)src, dst + (wave * NGH + i) * 1024);
       }
@@ -267,14 +196,14 @@ __global__ __launch_bounds__(512) void conv_halo_f32_kernel(const Halo32Args a) 
     }
   };
   mark();
-  Cur cur = cur_of(tile_begin), nxt = cur;
+  HaloCursor cur = halo_cursor_of(tile_begin, nfb, ntb), nxt = cur;
   int nxt_ch = 0, nxt_left = ntile_blk * nchunk;
   int buf = 0;
   if (nxt_left > 0) {
     issue(nxt, 0, 0);
     --nxt_left;
     nxt_ch = 1;
-    if (nxt_ch == nchunk) { nxt_ch = 0; advance(nxt); }
+    if (nxt_ch == nchunk) { nxt_ch = 0; nxt.advance(nfb, ntb); }
   }
   for (int ti = 0; ti < ntile_blk; ++ti) {
 #pragma unroll
@@ -298,7 +227,7 @@ __global__ __launch_bounds__(512) void conv_halo_f32_kernel(const Halo32Args a) 
       if (nxt_left > 0) {
         issue(nxt, nxt_ch, buf ^ 1);
         --nxt_left;
-        if (++nxt_ch == nchunk) { nxt_ch = 0; advance(nxt); }
+        if (++nxt_ch == nchunk) { nxt_ch = 0; nxt.advance(nfb, ntb); }
       }
       if (have_out) {
         flush();
@@ -379,46 +308,16 @@ __global__ __launch_bounds__(512) void conv_halo_f32_kernel(const Halo32Args a) 
       st_q[nb] += (double)sq;
     }
     have_out = true;
-    advance(cur);
+    cur.advance(nfb, ntb);
     mark();
   }
   if (have_out) flush();
   mark();
 
-  if (d.stats || a.f.acc) {  // workgroup partial: lanes (h halves) and waves in a fixed order
+  if (d.stats || a.f.acc) {  // workgroup partial: red[NW][NBW][2] over the halo buffers
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    double* red = reinterpret_cast<double*>(smem);  // reuse the halo buffers: [NW][NBW][2]
-#pragma unroll
-    for (int nb = 0; nb < NB; ++nb) {
-      const double s2 = st_s[nb] + __shfl_xor(st_s[nb], 32, 64);
-      const double q2 = st_q[nb] + __shfl_xor(st_q[nb], 32, 64);
-      if (h == 0) {
-        red[(wave * NBW + nb * 32 + l32) * 2] = s2;
-        red[(wave * NBW + nb * 32 + l32) * 2 + 1] = q2;
-      }
-    }
-    __syncthreads();
-    if (a.f.acc) {  // folded finalize: waves in the same fixed order
-      bnfold_commit(a.f, d.N, [&](int n, double& S, double& Q) {
-        S = 0.0;
-        Q = 0.0;
-        for (int w = 0; w < NW; ++w) {
-          S += red[(w * NBW + n) * 2];
-          Q += red[(w * NBW + n) * 2 + 1];
-        }
-      }, reinterpret_cast<int*>(red + NW * NBW * 2), blockIdx.x, gridDim.x);
-    } else if (blockIdx.x < a.nblk128) {
-      for (int n = tid; n < d.N; n += 512) {
-        double S = 0.0, Q = 0.0;
-        for (int w = 0; w < NW; ++w) {
-          S += red[(w * NBW + n) * 2];
-          Q += red[(w * NBW + n) * 2 + 1];
-        }
-        d.stats[((int64_t)blockIdx.x * a.stats_ld + n) * 2] = S;
-        d.stats[((int64_t)blockIdx.x * a.stats_ld + n) * 2 + 1] = Q;
-      }
-    }
+    halo_stats_commit<NW, NBW>(d, a.f, smem, st_s, st_q, wave, [&](int nb) { return nb * 32 + l32; }, 0,
+                               d.N, g.stats_ld, g.nblk128);
   }
 }
 
@@ -427,46 +326,21 @@ static bool halo32_plan(const clskd_conv_desc& d, Halo32Args& a, size_t& lds) {
   using namespace h32;
   if (d.in_dtype != CLSKD_F32 || d.compute != CLSKD_F32 || d.out_dtype != CLSKD_F32) return false;
   if (d.accumulate || d.wlayout != CLSKD_WLAYOUT_NK) return false;
-  if (d.N < 1 || d.N > 64 || d.ntaps < 1 || d.ntaps > 16 || d.stride_t != 1) return false;
+  if (d.N < 1 || d.N > 64 || d.stride_t != 1) return false;
   if (d.stride_f < 1 || d.stride_f > 2 || d.ctot < CW || d.ctot % CW) return false;
   a.d = d;
-  int nch = 0, kofs = 0;
-  for (int s = 0; s < d.nseg; ++s) {
+  if (!halo_geom_plan(d, CW, FT, TT, 1, 32, a.g)) return false;
+  for (int s = 0; s < d.nseg; ++s) {  // 16-B DMA sources
     const clskd_seg& g = d.seg[s];
-    if (d.seg_c[s] % CW) return false;
     if (((uintptr_t)g.ptr & 15) || g.sB % 4 || g.sF % 4 || g.sT % 4) return false;
-    if (g.sB > INT32_MAX || g.sF > INT32_MAX || g.sT > INT32_MAX) return false;
-    for (int c0 = 0; c0 < d.seg_c[s]; c0 += CW) {
-      if (nch >= MAXCH) return false;
-      a.chunk_seg[nch] = s;
-      a.chunk_c0[nch] = c0;
-      a.chunk_kofs[nch] = kofs + c0;
-      ++nch;
-    }
-    kofs += d.seg_c[s];
   }
-  if (kofs != d.ctot || d.ntaps * d.ctot > d.K || d.K % 4) return false;
+  if (d.ntaps * d.ctot > d.K || d.K % 4) return false;
   if (((uintptr_t)d.weight & 15)) return false;
-  a.nchunk = nch;
-  int dfmin = 1 << 20, dfmax = -(1 << 20), dtmin = 1 << 20, dtmax = -(1 << 20);
-  for (int t = 0; t < d.ntaps; ++t) {
-    dfmin = d.tap_df[t] < dfmin ? d.tap_df[t] : dfmin;
-    dfmax = d.tap_df[t] > dfmax ? d.tap_df[t] : dfmax;
-    dtmin = d.tap_dt[t] < dtmin ? d.tap_dt[t] : dtmin;
-    dtmax = d.tap_dt[t] > dtmax ? d.tap_dt[t] : dtmax;
-  }
-  a.dfmin = dfmin;
-  a.dtmin = dtmin;
-  a.HF = (FT - 1) * d.stride_f + (dfmax - dfmin + 1);
-  a.HT = (TT - 1) + (dtmax - dtmin + 1);
-  if (a.HF > 255 || a.HT > 255) return false;
-  a.NPIX = a.HF * a.HT;
-  for (int t = 0; t < 16; ++t) {
-    a.tap_pix[t] = t < d.ntaps ? (d.tap_df[t] - dfmin) * a.HT + (d.tap_dt[t] - dtmin) : 0;
-    a.tap_kq[t] = t < d.ntaps ? t * d.ctot / 4 : 0;
-  }
-  if (a.NPIX >= 65536 || (d.ntaps - 1) * d.ctot / 4 >= 32768) return false;
-  a.NGH = (int)cdiv((int64_t)a.NPIX * 2, 64 * NW);  // 2 x 16-B slots per pixel
+  halo_tap_pix(d, a.g, a.tap_pix);
+  for (int t = 0; t < 16; ++t) a.tap_kq[t] = t < d.ntaps ? t * d.ctot / 4 : 0;
+  // (the tap table packs pixel | k-quad << 16)
+  if (a.g.NPIX >= 65536 || (d.ntaps - 1) * d.ctot / 4 >= 32768) return false;
+  a.NGH = (int)cdiv((int64_t)a.g.NPIX * 2, 64 * NW);  // 2 x 16-B slots per pixel
   if (a.NGH > MAXG) return false;
   a.halo_bytes = NW * a.NGH * 1024;
   a.k4 = d.ntaps * d.ctot / 4;
@@ -474,27 +348,48 @@ static bool halo32_plan(const clskd_conv_desc& d, Halo32Args& a, size_t& lds) {
   lds = 2 * (size_t)a.halo_bytes + (size_t)a.k4 * NBW * 16 + 2 * MAXCH * 16 + 16 * 4;
   if (lds > 160 * 1024) return false;
   if ((d.stats || d.bn_fold) && (size_t)NW * NBW * 16 + 16 > 2 * (size_t)a.halo_bytes) return false;
-  a.nfb = (int)cdiv(d.Fo, FT);
-  a.ntb = (int)cdiv(d.To, TT);
-  const int64_t nt = (int64_t)d.B * a.nfb * a.ntb;
-  if (nt < 32 || nt > (1 << 30)) return false;
-  a.ntiles = (int)nt;
-  a.nblk128 = (int)cdiv((int64_t)d.B * d.Fo * d.To, 128);
-  a.stats_ld = d.N;
   a.f = make_bnfold(d);
   return true;
 }
 
-static int launch_halo32_planned(const Halo32Args& a, size_t lds, hipStream_t st, bool* launched) {
+static int halo32_grid(const Halo32Args& a) {
+  const int ncu = device_cu_count();
+  return a.g.ntiles < ncu ? a.g.ntiles : ncu;
+}
+
+// fp32 layers with 32 <= N <= 64 and the (tap, segment, channel) K structure whose weights fit
+// LDS beside the halo buffers and with at least one full 8-row F tile: the halo kernel;
+// false leaves the layer to the engine.  Measured on the student's C2 layers
+// (tools/conv_census.py): enc2 54 vs 60 us, enc3 83 vs 94, decoder 32-channel parities 107 / 80
+// vs 138 / 88.  Layers that need the two-launch column split (64 x K >= 512 weights) or have
+// Fo < 8 (half the waves idle) measured slower than the engine (e.g. the 4-row encoder layer 119
+// vs 64 us); CLSKD_HALO32_SPLIT=1 still takes them (the split path stays parity-tested).
+// Every condition under which the layer is not this kernel's is here; n: launches planned.
+static bool halo32_decide(const clskd_conv_desc& d, Halo32Args (&a)[2], size_t (&lds)[2], int& n) {
+  // 16-wide layers run with the 32-column block half idle (zero weight columns, masked stores);
+  // CLSKD_HALO32_MIN_N selects the narrowest N taken (A/B knob)
+  const int min_n = knob(KNOB_HALO32_MIN_N);
+  if (d.N < (min_n > 0 ? min_n : 32)) return false;
+  const bool split_ok = knob(KNOB_HALO32_SPLIT) == 1;
+  if (!split_ok && d.Fo < h32::FT) return false;
+  n = 1;
+  if (!halo32_plan(d, a[0], lds[0])) {
+    if (!split_ok || !halo_halves_plan(d, 4, 4, halo32_plan, a, lds)) return false;
+    n = 2;
+  }
+#ifdef CLSKD_EXPERIMENTS
+  if (const int dbg = knob(KNOB_H32_DEBUG_MODE))  // timing-only modes: the 64 x 10-tap shape alone
+    if (a[0].d.N <= 32 || d.ntaps != 10 || dbg < 1 || dbg > 9) return false;
+#endif
+  if (d.ntaps != 4 && d.ntaps != 6 && d.ntaps != 9 && d.ntaps != 10) return false;  // built tap counts
+  for (int i = 0; i < n; ++i)
+    if (a[i].d.stats && halo32_grid(a[i]) > a[i].g.nblk128) return false;  // (never for eligible shapes)
+  return true;
+}
+
+static void launch_halo32_planned(const Halo32Args& a, size_t lds, hipStream_t st) {
   const clskd_conv_desc& d = a.d;
-  *launched = false;
-  static int ncu = [] {
-    int v = 256;
-    (void)hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, 0);
-    return v > 0 ? v : 256;
-  }();
-  const int grid = a.ntiles < ncu ? a.ntiles : ncu;
-  if (d.stats && grid > a.nblk128) return CLSKD_OK;  // (never for eligible shapes)
+  const int grid = halo32_grid(a);
 #define H32_LAUNCH(NB_, NT_, ...)                                                              \
   do {                                                                                         \
     auto k = conv_halo_f32_kernel<NB_, NT_, ##__VA_ARGS__>;                                                 \
@@ -509,100 +404,45 @@ static int launch_halo32_planned(const Halo32Args& a, size_t lds, hipStream_t st
     if (d.N <= 32) H32_LAUNCH(1, NT_); else H32_LAUNCH(2, NT_);                                \
   } while (0)
 #ifdef CLSKD_EXPERIMENTS
-  if (const int dbg = knob(KNOB_H32_DEBUG_MODE)) {  // timing-only modes on the 64 x 10-tap shape
-    if (d.N <= 32 || d.ntaps != 10) return CLSKD_OK;
-    switch (dbg) {
-      case 1: H32_LAUNCH(2, 10, 1); break;
-      case 2: H32_LAUNCH(2, 10, 2); break;
-      case 3: H32_LAUNCH(2, 10, 3); break;
-      case 4: H32_LAUNCH(2, 10, 4); break;
-      case 5: H32_LAUNCH(2, 10, 5); break;
-      case 6: H32_LAUNCH(2, 10, 6); break;
-      case 7: H32_LAUNCH(2, 10, 7); break;
-      case 8: H32_LAUNCH(2, 10, 8); break;
-      case 9: H32_LAUNCH(2, 10, 9); break;
-      default: return CLSKD_OK;
-    }
-    *launched = true;
-    return CLSKD_OK;
+  switch (knob(KNOB_H32_DEBUG_MODE)) {  // (halo32_decide: N > 32, 10 taps)
+    case 0: break;
+    case 1: H32_LAUNCH(2, 10, 1); return;
+    case 2: H32_LAUNCH(2, 10, 2); return;
+    case 3: H32_LAUNCH(2, 10, 3); return;
+    case 4: H32_LAUNCH(2, 10, 4); return;
+    case 5: H32_LAUNCH(2, 10, 5); return;
+    case 6: H32_LAUNCH(2, 10, 6); return;
+    case 7: H32_LAUNCH(2, 10, 7); return;
+    case 8: H32_LAUNCH(2, 10, 8); return;
+    default: H32_LAUNCH(2, 10, 9); return;
   }
 #endif
-  switch (d.ntaps) {
+  switch (d.ntaps) {  // (halo32_decide: one of these)
     case 4: H32_NT(4); break;
     case 6: H32_NT(6); break;
     case 9: H32_NT(9); break;
-    case 10: H32_NT(10); break;
-    default: return CLSKD_OK;  // not a built tap count: engine path
+    default: H32_NT(10); break;
   }
 #undef H32_NT
 #undef H32_LAUNCH
-  *launched = true;
-  return CLSKD_OK;
 }
 
-// fp32 layers with 32 <= N <= 64 and the (tap, segment, channel) K structure whose weights fit
-// LDS beside the halo buffers and with at least one full 8-row F tile: the halo kernel;
-// *launched = false leaves the layer to the engine.  Measured on the student's C2 layers
-// (tools/conv_census.py): enc2 54 vs 60 us, enc3 83 vs 94, decoder 32-channel parities 107 / 80
-// vs 138 / 88.  Layers that need the two-launch column split (64 x K >= 512 weights) or have
-// Fo < 8 (half the waves idle) measured slower than the engine (e.g. the 4-row encoder layer 119
-// vs 64 us); CLSKD_HALO32_SPLIT=1 still takes them (the split path stays parity-tested).
-// Whether launch_conv_halo_f32 would take the layer (the same plans, nothing launched).
+// Whether launch_conv_halo_f32 would take the layer (the same decision, nothing launched).
 bool conv_halo_f32_takes(const clskd_conv_desc& d) {
-  Halo32Args a;
-  size_t lds = 0;
-  const int min_n = knob(KNOB_HALO32_MIN_N);
-  if (d.N < (min_n > 0 ? min_n : 32)) return false;
-  const bool split_ok = knob(KNOB_HALO32_SPLIT) == 1;
-  if (!split_ok && d.Fo < h32::FT) return false;
-  if (halo32_plan(d, a, lds)) return true;
-  if (!split_ok || d.N <= 32 || d.N > 64 || d.nlo < d.N) return false;
-  clskd_conv_desc d1 = d, d2 = d;
-  d1.N = 32;
-  d2.N = d.N - 32;
-  Halo32Args a2;
-  size_t lds2 = 0;
-  return halo32_plan(d1, a, lds) && halo32_plan(d2, a2, lds2);
+  Halo32Args a[2];
+  size_t lds[2] = {0, 0};
+  int n = 0;
+  return halo32_decide(d, a, lds, n);
 }
 
 int launch_conv_halo_f32(const clskd_conv_desc& d, hipStream_t st, bool* launched) {
-  Halo32Args a;
-  size_t lds = 0;
-  *launched = false;
-  // 16-wide layers run with the 32-column block half idle (zero weight columns, masked stores);
-  // CLSKD_HALO32_MIN_N selects the narrowest N taken (A/B knob)
-  const int min_n = knob(KNOB_HALO32_MIN_N);
-  if (d.N < (min_n > 0 ? min_n : 32)) return CLSKD_OK;
-  const bool split_ok = knob(KNOB_HALO32_SPLIT) == 1;
-  if (!split_ok && d.Fo < h32::FT) return CLSKD_OK;
-  if (halo32_plan(d, a, lds)) return launch_halo32_planned(a, lds, st, launched);
-  if (!split_ok || d.N <= 32 || d.N > 64 || d.nlo < d.N) return CLSKD_OK;
-  Halo32Args a2;
-  size_t lds2 = 0;
-  clskd_conv_desc d1 = d, d2 = d;
-  d1.N = 32;
-  d2.N = d.N - 32;
-  d2.weight = reinterpret_cast<const float*>(d.weight) + (int64_t)32 * d.K;
-  if (d.bias) d2.bias = d.bias + 32;
-  d2.out = reinterpret_cast<float*>(d.out) + (int64_t)32 * d.oNlo;
-  if (d.stats) d2.stats = d.stats + 64;
-  if (!halo32_plan(d1, a, lds) || !halo32_plan(d2, a2, lds2)) return CLSKD_OK;
-  a.stats_ld = a2.stats_ld = d.N;
-  if (a.f.acc) {  // column halves: the second one (channels +32) finalizes the layer
-    a2.f = a.f;
-    a.f.finalize = 0;
-    a2.f.c_off += 32;
-  }
-  bool l1 = false, l2 = false;
-  int rc = launch_halo32_planned(a, lds, st, &l1);
-  if (rc != CLSKD_OK || !l1) return rc;
-  rc = launch_halo32_planned(a2, lds2, st, &l2);
-  if (rc == CLSKD_OK && !l2) {
-    set_error("conv halo f32: second column half not launchable");
-    return CLSKD_E_ARG;
-  }
-  *launched = true;
-  return rc;
+  Halo32Args a[2];
+  size_t lds[2] = {0, 0};
+  int n = 0;
+  *launched = halo32_decide(d, a, lds, n);
+  if (*launched)
+    for (int i = 0; i < n; ++i) launch_halo32_planned(a[i], lds[i], st);
+  return CLSKD_OK;
 }
 
 }  // namespace clskd

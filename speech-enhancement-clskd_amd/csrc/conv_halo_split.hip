@@ -39,10 +39,12 @@
 //   workgroups of one launch keep the planes of columns [0, 32) / [32, N) resident (80 / 97 KiB)
 //   and walk the same tiles; the halo is staged and split by both halves, the folded BatchNorm
 //   finalize counts every workgroup of the launch (channel offset + 32 for the odd ones).
+//
+// The tile walk, the chunk table, the staging-slot word and the statistics reduction are
+// conv_halo_common.h's; clskd_conv_halo_split_plan walks the staging loads with the same helpers.
 #include <stdlib.h>
 
-#include "bnfold.h"
-#include "common.h"
+#include "conv_halo_common.h"
 
 namespace clskd {
 
@@ -52,49 +54,40 @@ typedef __attribute__((address_space(1))) float gfloat_hs3;
 
 namespace hs3 {
 typedef short s16x8 __attribute__((ext_vector_type(8)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
 constexpr int NW = 8;       // waves (= 32-row MFMA blocks of a tile)
-constexpr int NTH = NW * 64;
+constexpr int NTH = HALO_NTH;
 constexpr int MAXU = 6;     // 16-B staging loads per thread per chunk
-constexpr int MAXCH = 64;   // channel chunks (ctot <= 512 at CW = 8)
+constexpr int MAXCH = HALO_MAXCH;  // channel chunks (ctot <= 512 at CW = 8)
 constexpr int MAXSTEP = 16; // 16-deep MFMA steps per chunk
-
-// hi / lo bf16 split of 4 fp32 values (RNE both; the same arithmetic as sp3::split4)
-__device__ __forceinline__ void split4(const f32x4 v, s16x4& hi, s16x4& lo) {
-  bf16x4 h, l;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    h[i] = (__bf16)v[i];
-    l[i] = (__bf16)(v[i] - (float)h[i]);
-  }
-  hi = __builtin_bit_cast(s16x4, h);
-  lo = __builtin_bit_cast(s16x4, l);
-}
 
 // byte offset of k-quad q of pixel p inside a plane (CW 16: swizzled 16-B halves of 32-B rows)
 __host__ __device__ inline int plane_off(int cw, int p, int q) {
   return cw == 16 ? p * 32 + ((((q >> 1) ^ (p >> 3)) & 1) << 4) + (q & 1) * 8 : p * 16 + (q & 1) * 8;
 }
+
+// Staging slot i of thread tid: k-quad q of halo pixel p.  Returns the slot word (sub = q) and
+// the pixel whose plane offset the slot writes (0 for a slot past the halo: never written).
+__host__ __device__ __forceinline__ int stage_slot(int tid, int i, int qp, int NU, int NPIX, int HT,
+                                                   int& pp, int& q) {
+  const int u = tid + i * NTH;
+  const int p = u / qp;
+  q = u % qp;
+  const bool ok = i < NU && p < NPIX;
+  pp = ok ? p : 0;
+  return halo_slot_pack(p, q, ok, HT);
+}
 }  // namespace hs3
 
 struct HaloSplitArgs {
   clskd_conv_desc d;
-  int32_t nchunk;
-  int32_t chunk_seg[hs3::MAXCH];
-  int32_t chunk_c0[hs3::MAXCH];    // channel offset inside the segment
-  int32_t chunk_kofs[hs3::MAXCH];  // channel offset of the chunk inside one tap's ctot channels
+  HaloGeom g;
   int32_t cw, tw;                  // channels per chunk (8 | 16); 32-step T blocks per tile (1 | 2)
-  int32_t dfmin, dtmin;            // halo origin relative to (fo * stride_f, to)
-  int32_t HF, HT, NPIX;            // halo extent (pixels) and count
   int32_t NU;                      // staging loads per thread per chunk
   int32_t plane_bytes;             // bytes of one bf16 plane of the halo
   int32_t nstep;                   // 16-deep MFMA steps per chunk
   int32_t step_pix[2][hs3::MAXSTEP];  // halo pixel offset read by lane half h at step s
   int32_t step_oct[2][hs3::MAXSTEP];  // weight k-octet (chunk-relative; -1: the zero octet)
   int32_t koct;                    // k-octets of resident weights (ntaps * ctot / 8), + 1 zero octet
-  int32_t nfb, ntb, ntiles;        // tile grid: F-blocks, T-blocks, total
-  int32_t nblk128;                 // statistics slots (ceil(M / 128))
-  int32_t stats_ld;                // channels per statistics slot row
   int32_t nhalf;                   // 2: odd / even workgroups own output columns [0, 32) / [32, N)
   BnFoldArgs f;
 };
@@ -103,6 +96,7 @@ template <int NB, int CW, int NSTEP>
 __global__ __launch_bounds__(512) void conv_halo_split3_kernel(const HaloSplitArgs a) {
   using namespace hs3;
   const clskd_conv_desc& d = a.d;
+  const HaloGeom& g = a.g;
   constexpr int NBW = NB * 32;
   constexpr int QP = CW / 4;           // 16-B staging loads per pixel
   constexpr int NACC = NB == 1 ? 3 : 1;  // NB = 1: the cross terms on accumulators of their own
@@ -160,48 +154,31 @@ __global__ __launch_bounds__(512) void conv_halo_split3_kernel(const HaloSplitAr
       *reinterpret_cast<int2*>(wl + pl * wplane + a.koct * NBW * 16 + piece * 8) = make_int2(0, 0);
     }
   }
-  if (tid < a.nchunk) {
-    const clskd_seg& S = d.seg[a.chunk_seg[tid]];
-    const uint64_t base = (uint64_t)(uintptr_t)(S.ptr + a.chunk_c0[tid]);
-    ctA[tid] = make_int4((int)(unsigned)base, (int)(unsigned)(base >> 32), (int)S.sF, (int)S.sT);
-    ctB[tid] = make_int4((int)S.sB, S.F, S.T, a.chunk_kofs[tid]);
-  }
+  halo_ctab_fill(ctA, ctB, d, g, 4);
   if (d.stats) {  // slots no workgroup owns (grid <= nblk128) are zero
-    for (int64_t s = (int64_t)blockIdx.x + gridDim.x; s < a.nblk128; s += gridDim.x)
-      for (int i = tid; i < d.N * 2; i += NTH) d.stats[s * a.stats_ld * 2 + i] = 0.0;
+    halo_stats_zero_unowned(d.stats, d.N, g.stats_ld, g.nblk128);
     if (nhalf == 2)  // the other half's columns of this workgroup's own slot
       for (int i = tid; i < (d.N - N) * 2; i += NTH)
-        d.stats[((int64_t)blockIdx.x * a.stats_ld + (half ? 0 : 32)) * 2 + i] = 0.0;
+        d.stats[((int64_t)blockIdx.x * g.stats_ld + (half ? 0 : 32)) * 2 + i] = 0.0;
   }
   float bcol[NB];
   int64_t coff[NB];
-#pragma unroll
-  for (int nb = 0; nb < NB; ++nb) {
-    const int n = nb * 32 + l32;
-    const int ng = n0 + n;
-    bcol[nb] = (d.bias && n < N) ? d.bias[ng] : 0.f;
-    coff[nb] = n < N ? (int64_t)(ng / d.nlo) * d.oNhi + (int64_t)(ng % d.nlo) * d.oNlo : -1;
-  }
-  const int nchunk = a.nchunk, ntb = a.ntb, nfb = a.nfb, NU = a.NU;
+  halo_bias_coff<NB, false>(d, n0, N, l32, bcol, coff);
+  const int nchunk = g.nchunk, ntb = g.ntb, nfb = g.nfb, NU = a.NU;
   const int tw = a.tw, FT = NW / tw, TT = 32 * tw;
   const int Fo = d.Fo, To = d.To, sfr = d.stride_f;
-  const int dfmin = a.dfmin, dtmin = a.dtmin;
+  const int dfmin = g.dfmin, dtmin = g.dtmin;
   const int64_t oB = d.oB, oF = d.oF, oT = d.oT;
   const int of_mul = d.of_mul, of_add = d.of_add;
   gfloat_hs3* const outp = reinterpret_cast<gfloat_hs3*>((uintptr_t)d.out);
-  // per-thread staging slots: halo pixel (hf, ht), k-quad, LDS offset; packed hf | ht << 8 |
-  // quad << 16 | valid << 20
+  // per-thread staging slots: the slot word (sub = k-quad) and the LDS offset it writes
   int ug[MAXU], uo[MAXU];
   {
-    const int HT = a.HT, NPIX = a.NPIX;
+    const int HT = g.HT, NPIX = g.NPIX;
 #pragma unroll
     for (int i = 0; i < MAXU; ++i) {
-      const int u = tid + i * NTH;
-      const int p = u / QP, q = u % QP;
-      const bool ok = i < NU && p < NPIX;
-      const int pp = ok ? p : 0;
-      const int hf = pp / HT, ht = pp - hf * HT;
-      ug[i] = hf | (ht << 8) | (q << 16) | ((ok ? 1 : 0) << 20);
+      int pp, q;
+      ug[i] = stage_slot(tid, i, QP, NU, NPIX, HT, pp, q);
       uo[i] = plane_off(CW, pp, q);
     }
   }
@@ -211,7 +188,7 @@ __global__ __launch_bounds__(512) void conv_halo_split3_kernel(const HaloSplitAr
   int sa[NSTEP];
   unsigned sb[NSTEP];
   {
-    const int prow0 = frow * sfr * a.HT + tblk * 32 + l32;
+    const int prow0 = frow * sfr * g.HT + tblk * 32 + l32;
 #pragma unroll
     for (int s = 0; s < NSTEP; ++s) {
       const int p = prow0 + (h ? a.step_pix[1][s] : a.step_pix[0][s]);
@@ -223,44 +200,24 @@ __global__ __launch_bounds__(512) void conv_halo_split3_kernel(const HaloSplitAr
   }
   __syncthreads();
 
-  const int per = (a.ntiles + nwg - 1) / nwg;
+  const int per = (g.ntiles + nwg - 1) / nwg;
   const int tile_begin = wgi * per;
-  const int ntile_blk = max(0, min(a.ntiles, tile_begin + per) - tile_begin);
-
-  struct Cur { int b, fb, tb; };
-  auto cur_of = [&](int tile) {
-    Cur c;
-    c.tb = tile % ntb;
-    const int r = tile / ntb;
-    c.fb = r % nfb;
-    c.b = r / nfb;
-    return c;
-  };
-  auto advance = [&](Cur& c) {
-    if (++c.tb == ntb) {
-      c.tb = 0;
-      if (++c.fb == nfb) { c.fb = 0; ++c.b; }
-    }
-  };
+  const int ntile_blk = max(0, min(g.ntiles, tile_begin + per) - tile_begin);
 
   f32x4 ra[MAXU];
   // global loads of one chunk's halo into registers: out-of-range pixels are zero (a select,
   // never a load)
-  auto load_chunk = [&](const Cur& c, int ch) {
-    const int4 ea = ctA[ch];
-    const int4 eb = ctB[ch];
-    const float* base = reinterpret_cast<const float*>(((uint64_t)(unsigned)ea.y << 32) | (unsigned)ea.x) +
-                        (int64_t)c.b * eb.x;
+  auto load_chunk = [&](const HaloCursor& c, int ch) {
+    const HaloChunk<float> k = halo_chunk<float>(ctA, ctB, ch);
+    const float* base = k.base + (int64_t)c.b * k.sB;
     const int fi_lo = c.fb * FT * sfr + dfmin, ti_lo = c.tb * TT + dtmin;
 #pragma unroll
     for (int i = 0; i < MAXU; ++i) {
       if (i < NU) {
-        const int g = ug[i];
-        const int fi = fi_lo + (g & 0xff), ti = ti_lo + ((g >> 8) & 0xff);
+        bool ok;
+        const HaloSlotSrc s = halo_slot_src(ug[i], fi_lo, ti_lo, k.F, k.T, ok);
         f32x4 v = {0.f, 0.f, 0.f, 0.f};
-        if (((g >> 20) & 1) && (unsigned)fi < (unsigned)eb.y && (unsigned)ti < (unsigned)eb.z)
-          v = *reinterpret_cast<const f32x4*>(base + (int64_t)fi * ea.z + (int64_t)ti * ea.w +
-                                              ((g >> 16) & 3) * 4);
+        if (ok) v = *reinterpret_cast<const f32x4*>(base + (int64_t)s.fi * k.sF + (int64_t)s.ti * k.sT + s.sub * 4);
         ra[i] = v;
       }
     }
@@ -286,10 +243,10 @@ __global__ __launch_bounds__(512) void conv_halo_split3_kernel(const HaloSplitAr
   // chunk stream over this workgroup's tiles: chunk it computes from buffer it & 1 while chunk
   // it + 1 (loaded one round ago) is split into the other buffer and chunk it + 2 is loaded
   const int total = ntile_blk * nchunk;
-  Cur cur = cur_of(tile_begin), nxt = cur;
+  HaloCursor cur = halo_cursor_of(tile_begin, nfb, ntb), nxt = cur;
   int nxt_ch = 0;
   auto step_next = [&]() {
-    if (++nxt_ch == nchunk) { nxt_ch = 0; advance(nxt); }
+    if (++nxt_ch == nchunk) { nxt_ch = 0; nxt.advance(nfb, ntb); }
   };
   if (total > 0) {
     load_chunk(nxt, nxt_ch);
@@ -370,43 +327,14 @@ __global__ __launch_bounds__(512) void conv_halo_split3_kernel(const HaloSplitAr
       st_s[nb] += (double)sm;
       st_q[nb] += (double)sq;
     }
-    advance(cur);
+    cur.advance(nfb, ntb);
   }
 
-  if (d.stats || a.f.acc) {  // workgroup partial: lane halves, then waves in a fixed order
-    __syncthreads();
-    double* red = reinterpret_cast<double*>(smem);  // reuse the halo buffers: [NW][NBW][2]
-#pragma unroll
-    for (int nb = 0; nb < NB; ++nb) {
-      const double s2 = st_s[nb] + __shfl_xor(st_s[nb], 32, 64);
-      const double q2 = st_q[nb] + __shfl_xor(st_q[nb], 32, 64);
-      if (h == 0) {
-        red[(wave * NBW + nb * 32 + l32) * 2] = s2;
-        red[(wave * NBW + nb * 32 + l32) * 2 + 1] = q2;
-      }
-    }
-    __syncthreads();
-    auto sum_waves = [&](int n, double& S, double& Q) {
-      S = 0.0;
-      Q = 0.0;
-      for (int w = 0; w < NW; ++w) {
-        S += red[(w * NBW + n) * 2];
-        Q += red[(w * NBW + n) * 2 + 1];
-      }
-    };
-    if (a.f.acc) {
-      BnFoldArgs f = a.f;
-      f.c_off += n0;
-      bnfold_commit(f, N, sum_waves, reinterpret_cast<int*>(red + NW * NBW * 2), blockIdx.x,
-                    gridDim.x);
-    } else if (blockIdx.x < a.nblk128) {
-      for (int n = tid; n < N; n += NTH) {
-        double S, Q;
-        sum_waves(n, S, Q);
-        d.stats[((int64_t)blockIdx.x * a.stats_ld + n0 + n) * 2] = S;
-        d.stats[((int64_t)blockIdx.x * a.stats_ld + n0 + n) * 2 + 1] = Q;
-      }
-    }
+  if (d.stats || a.f.acc) {  // workgroup partial: red[NW][NBW][2] over the halo buffers
+    BnFoldArgs f = a.f;
+    f.c_off += n0;
+    halo_stats_commit<NW, NBW>(d, f, smem, st_s, st_q, wave, [&](int nb) { return nb * 32 + l32; }, n0, N,
+                               g.stats_ld, g.nblk128);
   }
 }
 
@@ -429,70 +357,41 @@ static bool halo_split_plan1(const clskd_conv_desc& d, HaloSplitArgs& a, size_t&
   using namespace hs3;
   if (d.in_dtype != CLSKD_F32 || d.compute != CLSKD_F32 || d.out_dtype != CLSKD_F32) return false;
   if (d.accumulate || d.wlayout != CLSKD_WLAYOUT_NK) return false;
-  if (d.N < 16 || d.N > 64 || d.ntaps < 1 || d.ntaps > 16 || d.stride_t != 1) return false;
+  if (d.N < 16 || d.N > 64 || d.stride_t != 1) return false;
   if (d.stride_f < 1 || d.stride_f > 2 || d.ctot < cw || d.ctot % cw) return false;
   if (d.nseg < 1 || d.nseg > CLSKD_MAX_SEGS) return false;
   a.d = d;
   a.cw = cw;
-  int nch = 0, kofs = 0;
-  for (int s = 0; s < d.nseg; ++s) {
+  for (int s = 0; s < d.nseg; ++s) {  // 16-B loads of every segment's channel runs
     const clskd_seg& g = d.seg[s];
-    if (d.seg_c[s] < cw || d.seg_c[s] % cw) return false;
+    if (d.seg_c[s] < cw) return false;
     if (((uintptr_t)g.ptr & 15) || g.sB % 4 || g.sF % 4 || g.sT % 4) return false;
     if (g.sB < 0 || g.sF < 0 || g.sT < 0) return false;
-    if (g.sB > INT32_MAX || g.sF > INT32_MAX || g.sT > INT32_MAX) return false;
-    for (int c0 = 0; c0 < d.seg_c[s]; c0 += cw) {
-      if (nch >= MAXCH) return false;
-      a.chunk_seg[nch] = s;
-      a.chunk_c0[nch] = c0;
-      a.chunk_kofs[nch] = kofs + c0;
-      ++nch;
-    }
-    kofs += d.seg_c[s];
-  }
-  if (kofs != d.ctot || d.ntaps * d.ctot > d.K || d.K % 8) return false;
-  if (((uintptr_t)d.weight & 15)) return false;
-  a.nchunk = nch;
-  int dfmin = 1 << 20, dfmax = -(1 << 20), dtmin = 1 << 20, dtmax = -(1 << 20);
-  for (int t = 0; t < d.ntaps; ++t) {
-    dfmin = d.tap_df[t] < dfmin ? d.tap_df[t] : dfmin;
-    dfmax = d.tap_df[t] > dfmax ? d.tap_df[t] : dfmax;
-    dtmin = d.tap_dt[t] < dtmin ? d.tap_dt[t] : dtmin;
-    dtmax = d.tap_dt[t] > dtmax ? d.tap_dt[t] : dtmax;
   }
   a.tw = d.Fo <= 4 ? 2 : 1;  // 4 F-rows x 64 steps: all eight waves work on a 4-row layer
-  const int FT = NW / a.tw, TT = 32 * a.tw;
-  a.dfmin = dfmin;
-  a.dtmin = dtmin;
-  a.HF = (FT - 1) * d.stride_f + (dfmax - dfmin + 1);
-  a.HT = (TT - 1) + (dtmax - dtmin + 1);
-  if (a.HF > 255 || a.HT > 255) return false;
-  a.NPIX = a.HF * a.HT;
-  a.NU = (int)cdiv((int64_t)a.NPIX * (cw / 4), NTH);
+  if (!halo_geom_plan(d, cw, NW / a.tw, 32 * a.tw, 1, 32, a.g)) return false;
+  if (d.ntaps * d.ctot > d.K || d.K % 8) return false;
+  if (((uintptr_t)d.weight & 15)) return false;
+  a.NU = (int)cdiv((int64_t)a.g.NPIX * (cw / 4), NTH);
   if (a.NU > MAXU) return false;
-  a.plane_bytes = (a.NPIX * cw * 2 + 15) & ~15;
+  a.plane_bytes = (a.g.NPIX * cw * 2 + 15) & ~15;
   a.koct = d.ntaps * d.ctot / 8;
   a.nstep = cw == 16 ? d.ntaps : (d.ntaps + 1) / 2;
   if (a.nstep > MAXSTEP) return false;
+  int32_t tap_pix[16];
+  halo_tap_pix(d, a.g, tap_pix);
   for (int h = 0; h < 2; ++h)
     for (int s = 0; s < MAXSTEP; ++s) {
       // CW 16: both lane halves read tap s (channel octets 0 / 1 of the chunk); CW 8: taps 2s, 2s+1
       const int t = cw == 16 ? s : 2 * s + h;
       const bool on = s < a.nstep && t < d.ntaps;
-      a.step_pix[h][s] = on ? (d.tap_df[t] - dfmin) * a.HT + (d.tap_dt[t] - dtmin) : 0;
+      a.step_pix[h][s] = on ? tap_pix[t] : 0;
       a.step_oct[h][s] = on ? t * (d.ctot / 8) + (cw == 16 ? h : 0) : -1;
     }
   const int NBW = d.N <= 32 ? 32 : 64;
   lds = 4 * (size_t)a.plane_bytes + 2 * (size_t)(a.koct + 1) * NBW * 16 + 2 * MAXCH * 16;
   if (lds > 160 * 1024) return false;
   if ((size_t)NW * NBW * 16 + 16 > 4 * (size_t)a.plane_bytes) return false;  // statistics scratch
-  a.nfb = (int)cdiv(d.Fo, FT);
-  a.ntb = (int)cdiv(d.To, TT);
-  const int64_t nt = (int64_t)d.B * a.nfb * a.ntb;
-  if (nt < 32 || nt > (1 << 30)) return false;
-  a.ntiles = (int)nt;
-  a.nblk128 = (int)cdiv((int64_t)d.B * d.Fo * d.To, 128);
-  a.stats_ld = d.N;
   a.nhalf = 1;
   a.f = make_bnfold(d);
   return true;
@@ -504,47 +403,46 @@ static bool halo_split_plan(const clskd_conv_desc& d, HaloSplitArgs& a, size_t& 
   return halo_split_plan1(d, a, lds, 16) || halo_split_plan1(d, a, lds, 8);
 }
 
-// Whole plan of a descriptor.  When the [64][K] weight planes do not fit beside the halo buffers
-// the launch runs as two column halves (nhalf = 2): even / odd workgroups keep the weight planes
-// of columns [0, 32) / [32, N) resident and walk the same tile list — one launch, one prologue per
-// workgroup; the halo is staged and split by both halves.
-static bool halo_split_plans(const clskd_conv_desc& d, HaloSplitArgs& a, size_t& lds) {
+static bool halo_split_built(const HaloSplitArgs& a) {
+  const int n = a.nstep;
+  return a.cw == 16 ? (n == 4 || n == 6 || n == 9 || n == 10) : (n == 2 || n == 3 || n == 5);
+}
+
+// Every condition under which the layer is not this kernel's (conv_split3_kernel runs it): the
+// knob, the plan, a built tap count.  When the [64][K] weight planes do not fit beside the halo
+// buffers the launch runs as two column halves (nhalf = 2): even / odd workgroups keep the weight
+// planes of columns [0, 32) / [32, N) resident and walk the same tile list — one launch, one
+// prologue per workgroup; the halo is staged and split by both halves.  (The grid is cut to the
+// statistics slots, halo_split_grid: no statistics condition declines.)
+static bool halo_split_decide(const clskd_conv_desc& d, HaloSplitArgs& a, size_t& lds) {
   if (knob(KNOB_HALO_SPLIT) != 1) return false;
-  if (halo_split_plan(d, a, lds)) return true;
-  if (d.N <= 32 || d.N > 64) return false;
-  clskd_conv_desc d1 = d, d2 = d;
-  d1.N = 32;
-  d2.N = d.N - 32;
-  HaloSplitArgs a2;
-  size_t lds2 = 0;
-  if (!halo_split_plan(d2, a2, lds2) || !halo_split_plan(d1, a, lds)) return false;
-  if (a2.cw != a.cw || lds2 != lds) return false;  // (same geometry: never)
-  a.d = d;
-  a.stats_ld = d.N;
-  a.nhalf = 2;
-  return true;
+  if (!halo_split_plan(d, a, lds)) {
+    if (d.N <= 32 || d.N > 64) return false;
+    clskd_conv_desc d1 = d, d2 = d;
+    d1.N = 32;
+    d2.N = d.N - 32;
+    HaloSplitArgs a2;
+    size_t lds2 = 0;
+    if (!halo_split_plan(d2, a2, lds2) || !halo_split_plan(d1, a, lds)) return false;
+    if (a2.cw != a.cw || lds2 != lds) return false;  // (same geometry: never)
+    a.d = d;
+    a.g.stats_ld = d.N;
+    a.nhalf = 2;
+  }
+  return halo_split_built(a);  // not a built tap count: conv_split3_kernel
 }
 
 static int halo_split_grid(const HaloSplitArgs& a) {
-  static int ncu = [] {
-    int v = 256;
-    (void)hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, 0);
-    return v > 0 ? v : 256;
-  }();
+  const int ncu = device_cu_count();
   // CLSKD_SPLIT_GRID caps the CUs the grid spans (tests: many tiles per workgroup)
   const int gcap = knob(KNOB_SPLIT_GRID);
   int cus = gcap > 0 && gcap < ncu ? gcap : ncu;
   const int own = knob(KNOB_HALO_SPLIT_GRID);  // this kernel's own span (0: every CU)
   if (own > 0 && own < cus) cus = own;
   int nwg = cus / a.nhalf;
-  nwg = a.ntiles < nwg ? a.ntiles : nwg;
-  if (a.d.stats && nwg * a.nhalf > a.nblk128) nwg = a.nblk128 / a.nhalf;  // a statistics slot each
+  nwg = a.g.ntiles < nwg ? a.g.ntiles : nwg;
+  if (a.d.stats && nwg * a.nhalf > a.g.nblk128) nwg = a.g.nblk128 / a.nhalf;  // a statistics slot each
   return (nwg > 0 ? nwg : 1) * a.nhalf;
-}
-
-static bool halo_split_built(const HaloSplitArgs& a) {
-  const int n = a.nstep;
-  return a.cw == 16 ? (n == 4 || n == 6 || n == 9 || n == 10) : (n == 2 || n == 3 || n == 5);
 }
 
 static void launch_halo_split_planned(const HaloSplitArgs& a, size_t lds, hipStream_t st) {
@@ -580,22 +478,17 @@ static void launch_halo_split_planned(const HaloSplitArgs& a, size_t lds, hipStr
 #undef HS3_LAUNCH
 }
 
-static bool halo_split_taken(const clskd_conv_desc& d, HaloSplitArgs& a, size_t& lds) {
-  // not a built tap count: conv_split3_kernel
-  return halo_split_plans(d, a, lds) && halo_split_built(a);
-}
-
-// Whether launch_conv_halo_split would take the layer (the same plan, nothing launched).
+// Whether launch_conv_halo_split would take the layer (the same decision, nothing launched).
 bool conv_halo_split_takes(const clskd_conv_desc& d) {
   HaloSplitArgs a;
   size_t lds = 0;
-  return halo_split_taken(d, a, lds);
+  return halo_split_decide(d, a, lds);
 }
 
 int launch_conv_halo_split(const clskd_conv_desc& d, hipStream_t st, bool* launched) {
   HaloSplitArgs a;
   size_t lds = 0;
-  *launched = halo_split_taken(d, a, lds);
+  *launched = halo_split_decide(d, a, lds);
   if (*launched) launch_halo_split_planned(a, lds, st);
   return CLSKD_OK;
 }
@@ -604,7 +497,8 @@ int launch_conv_halo_split(const clskd_conv_desc& d, hipStream_t st, bool* launc
 
 // The plan of a descriptor, for checking before anything runs: the tile grid, the halo, the LDS
 // footprint and — by walking every tile, chunk and staging slot with the kernel's own index
-// arithmetic — the smallest and largest element offset the staging loads touch per segment.
+// arithmetic (the cursor and slot helpers the kernel uses) — the smallest and largest element
+// offset the staging loads touch per segment.
 extern "C" int clskd_conv_halo_split_plan(const clskd_conv_desc* dp, clskd_halo_split_info* info) {
   using namespace clskd;
   using namespace clskd::hs3;
@@ -612,50 +506,53 @@ extern "C" int clskd_conv_halo_split_plan(const clskd_conv_desc* dp, clskd_halo_
   memset(info, 0, sizeof(*info));
   clskd_conv_desc d = *dp;
   if (d.compute == CLSKD_F32X3) d.compute = CLSKD_F32;
-  HaloSplitArgs a;
+  HaloSplitArgs p;
   size_t lds = 0;
-  if (!halo_split_taken(d, a, lds)) return CLSKD_OK;
+  if (!halo_split_decide(d, p, lds)) return CLSKD_OK;
+  const HaloGeom& g = p.g;
+  const int QP = p.cw / 4, FT = NW / p.tw, TT = 32 * p.tw;
   info->launches = 1;
-  info->col_halves = a.nhalf;
+  info->col_halves = p.nhalf;
+  info->cw = p.cw;
+  info->tile_f = FT;
+  info->tile_t = TT;
+  info->nfb = g.nfb;
+  info->ntb = g.ntb;
+  info->ntiles = g.ntiles;
+  info->halo_f = g.HF;
+  info->halo_t = g.HT;
+  info->nchunk = g.nchunk;
+  info->nstep = p.nstep;
+  info->lds_bytes = (int64_t)lds;
+  info->grid = halo_split_grid(p);
   for (int s = 0; s < CLSKD_MAX_SEGS; ++s) {
     info->seg_min_off[s] = INT64_MAX;
     info->seg_max_off[s] = INT64_MIN;
   }
-  {
-    const HaloSplitArgs& p = a;
-    info->cw = p.cw;
-    info->tile_f = NW / p.tw;
-    info->tile_t = 32 * p.tw;
-    info->nfb = p.nfb;
-    info->ntb = p.ntb;
-    info->ntiles = p.ntiles;
-    info->halo_f = p.HF;
-    info->halo_t = p.HT;
-    info->nchunk = p.nchunk;
-    info->nstep = p.nstep;
-    info->lds_bytes = (int64_t)lds;
-    info->grid = halo_split_grid(p);
-    const int QP = p.cw / 4, FT = NW / p.tw, TT = 32 * p.tw;
-    for (int s = 0; s < p.nstep; ++s)
-      for (int h = 0; h < 2; ++h) {  // the farthest fragment read stays inside the plane
-        const int pmax = (FT - 1) * p.d.stride_f * p.HT + (p.tw - 1) * 32 + 31 + p.step_pix[h][s];
-        CLSKD_CHECK_ARG(pmax < p.NPIX, "halo_split_plan: fragment pixel %d outside the halo %d", pmax, p.NPIX);
-      }
-    for (int tile = 0; tile < p.ntiles; ++tile) {
-      const int tb = tile % p.ntb, fb = (tile / p.ntb) % p.nfb, b = tile / p.ntb / p.nfb;
-      const int fi_lo = fb * FT * p.d.stride_f + p.dfmin, ti_lo = tb * TT + p.dtmin;
-      for (int ch = 0; ch < p.nchunk; ++ch) {
-        const int sg = p.chunk_seg[ch];
-        const clskd_seg& S = p.d.seg[sg];
-        for (int u = 0; u < p.NU * NTH; ++u) {
-          const int px = u / QP, q = u % QP;
-          if (px >= p.NPIX) continue;
-          const int fi = fi_lo + px / p.HT, ti = ti_lo + px % p.HT;
-          if ((unsigned)fi >= (unsigned)S.F || (unsigned)ti >= (unsigned)S.T) continue;
-          const int64_t off = p.chunk_c0[ch] + (int64_t)b * S.sB + (int64_t)fi * S.sF + (int64_t)ti * S.sT + q * 4;
-          if (off < info->seg_min_off[sg]) info->seg_min_off[sg] = off;
-          if (off + 3 > info->seg_max_off[sg]) info->seg_max_off[sg] = off + 3;
-        }
+  for (int s = 0; s < p.nstep; ++s)
+    for (int h = 0; h < 2; ++h) {  // the farthest fragment read stays inside the plane
+      const int pmax = (FT - 1) * p.d.stride_f * g.HT + (p.tw - 1) * 32 + 31 + p.step_pix[h][s];
+      CLSKD_CHECK_ARG(pmax < g.NPIX, "halo_split_plan: fragment pixel %d outside the halo %d", pmax, g.NPIX);
+    }
+  int ug[MAXU * NTH];  // the slot words of every thread, as the kernel packs them
+  for (int i = 0; i < MAXU; ++i)
+    for (int tid = 0; tid < NTH; ++tid) {
+      int pp, q;
+      ug[i * NTH + tid] = stage_slot(tid, i, QP, p.NU, g.NPIX, g.HT, pp, q);
+    }
+  HaloCursor c = halo_cursor_of(0, g.nfb, g.ntb);
+  for (int tile = 0; tile < g.ntiles; ++tile, c.advance(g.nfb, g.ntb)) {
+    const int fi_lo = c.fb * FT * p.d.stride_f + g.dfmin, ti_lo = c.tb * TT + g.dtmin;
+    for (int ch = 0; ch < g.nchunk; ++ch) {
+      const int sg = g.chunk_seg[ch];
+      const clskd_seg& S = p.d.seg[sg];
+      for (int u = 0; u < p.NU * NTH; ++u) {
+        bool ok;
+        const HaloSlotSrc s = halo_slot_src(ug[u], fi_lo, ti_lo, S.F, S.T, ok);
+        if (!ok) continue;
+        const int64_t off = g.chunk_c0[ch] + (int64_t)c.b * S.sB + (int64_t)s.fi * S.sF + (int64_t)s.ti * S.sT + s.sub * 4;
+        if (off < info->seg_min_off[sg]) info->seg_min_off[sg] = off;
+        if (off + 3 > info->seg_max_off[sg]) info->seg_max_off[sg] = off + 3;
       }
     }
   }

@@ -26,10 +26,12 @@
 // Staged bytes per 256x256x32 step: 16 KB weights + ~4 KB of input (a 40 KB halo per 10 taps)
 // against 32 KB in conv_gemm8.  Same descriptor contract (K ordered tap, segment, channel;
 // ntaps / ctot / seg_c / tap_df / tap_dt given), output map, bias and statistics semantics.
+// The plan's geometry, the tile cursor and the chunk table are conv_halo_common.h's.  The
+// statistics zeroing and reduction keep their own form here: through the shared helpers the
+// 256-column instances measured 2-5 us slower (profiles/halo_common_micro.txt).
 #include <stdlib.h>
 
-#include "bnfold.h"
-#include "common.h"
+#include "conv_halo_common.h"
 
 namespace clskd {
 
@@ -39,26 +41,9 @@ namespace hw {
 constexpr int NW = 8;      // waves
 constexpr int CW = 32;     // channels per chunk: 64-B pixel / weight rows
 constexpr int MAXG = 7;    // halo DMA instructions per wave per chunk
-constexpr int MAXCH = 32;  // chunks
+constexpr int MAXCH = 32;  // chunks (the LDS chunk table)
 constexpr int BST = 3;     // weight-slab ring stages (two steps in flight)
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ void glds16(const void* gsrc, unsigned lds_base) {
-  unsigned keep;
-  asm volatile(
-      "s_mov_b32 %0, m0\n\t"
-      "s_mov_b32 m0, %2\n\t"
-      "s_nop 0\n\t"
-      "global_load_lds_dwordx4 %1, off\n\t"
-      "s_mov_b32 m0, %0"
-      : "=&s"(keep)
-      : "v"(gsrc), "s"(lds_base)
-      : "memory");
-}
-
-__device__ __forceinline__ unsigned lds_addr(const void* p) {
-  return (unsigned)(uintptr_t)(const __attribute__((address_space(3))) char*)p;
-}
 
 __device__ __forceinline__ int swz(int r) { return (r >> 2) & 3; }  // 64-B rows, 16-B chunks
 
@@ -81,28 +66,13 @@ __device__ __forceinline__ void raw_barrier() {
   __builtin_amdgcn_sched_barrier(0);
 }
 
-__device__ __forceinline__ int sconst(int v) {
-  asm volatile("" : "+v"(v));
-  return __builtin_amdgcn_readfirstlane(v);
-}
-__device__ __forceinline__ int64_t vconst64(int64_t v) {
-  asm volatile("" : "+v"(v));
-  return v;
-}
 }  // namespace hw
 
 struct HwArgs {
   clskd_conv_desc d;
-  int32_t nchunk;
-  int32_t chunk_seg[hw::MAXCH];
-  int32_t chunk_c0[hw::MAXCH];    // channel offset inside the segment
-  int32_t chunk_kofs[hw::MAXCH];  // k offset of the chunk inside one tap's ctot channels
-  int32_t dfmin, dtmin;           // halo origin relative to (fo*stride_f, to)
-  int32_t HF, HT, NPIX;           // halo extent (pixels) and count
+  HaloGeom g;
   int32_t NGH;                    // halo DMA wave-instructions per wave per chunk
   int32_t halo_bytes;             // bytes per halo buffer (ceil(NPIX / 16) KiB)
-  int32_t nfb, ntb, ntiles;       // tile grid: F-blocks, T-blocks, total
-  int32_t nblk128;                // statistics slots (ceil(M/128))
   int32_t tap_pix[16];            // halo pixel offset of tap t for output (0, 0)
   int32_t vec;                    // 16-B output row chunks (channel-contiguous, aligned output)
   BnFoldArgs f;
@@ -133,6 +103,7 @@ __global__ __launch_bounds__(512) void conv_halow_kernel(const HwArgs a) {
   static_assert(FM >= 1 && FN >= 1 && GB >= 1 && WM * WN == NW, "tile split");
   static_assert(NTAPS >= 3 && NTAPS <= 16, "taps");
   const clskd_conv_desc& d = a.d;
+  const HaloGeom& g = a.g;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int halo_bytes = __builtin_amdgcn_readfirstlane(a.halo_bytes);
   unsigned char* hbuf = smem;                                    // [2][halo_bytes]
@@ -150,13 +121,7 @@ __global__ __launch_bounds__(512) void conv_halow_kernel(const HwArgs a) {
   const int wm = wave / WN, wn = wave % WN;
   const int l32 = lane & 31, h = lane >> 5;
 
-  if (tid < a.nchunk) {
-    const int sg = a.chunk_seg[tid];
-    const clskd_seg& S = d.seg[sg];
-    const uint64_t base = (uint64_t)(uintptr_t)(reinterpret_cast<const InT*>(S.ptr) + a.chunk_c0[tid]);
-    ctA[tid] = make_int4((int)(unsigned)base, (int)(unsigned)(base >> 32), (int)S.sF, (int)S.sT);
-    ctB[tid] = make_int4((int)S.sB, S.F, S.T, a.chunk_kofs[tid]);
-  }
+  halo_ctab_fill(ctA, ctB, d, g, 2);
   if (tid < 16) ttab[tid] = a.tap_pix[tid];
   if (tid == 0) {
     HwConsts c;
@@ -168,15 +133,15 @@ __global__ __launch_bounds__(512) void conv_halow_kernel(const HwArgs a) {
     c.To = d.To;
     c.of_mul = d.of_mul;
     c.of_add = d.of_add;
-    c.nchunk = a.nchunk;
-    c.ntb = a.ntb;
-    c.nfb = a.nfb;
+    c.nchunk = g.nchunk;
+    c.ntb = g.ntb;
+    c.nfb = g.nfb;
     c.NGH = a.NGH;
-    c.NPIX = a.NPIX;
-    c.HT = a.HT;
+    c.NPIX = g.NPIX;
+    c.HT = g.HT;
     c.sfr = d.stride_f;
-    c.dfmin = a.dfmin;
-    c.dtmin = a.dtmin;
+    c.dfmin = g.dfmin;
+    c.dtmin = g.dtmin;
     c.ctot = d.ctot;
     c.K = d.K;
     c.N = d.N;
@@ -185,15 +150,15 @@ __global__ __launch_bounds__(512) void conv_halow_kernel(const HwArgs a) {
   }
   for (int n = tid; n < BN; n += 512) {
     bias_l[n] = (d.bias && n < d.N) ? d.bias[n] : 0.f;
-    coff_l[n] = n < d.N ? (int64_t)(n / d.nlo) * d.oNhi + (int64_t)(n % d.nlo) * d.oNlo : -1;
+    coff_l[n] = n < d.N ? halo_col_off(d, n) : -1;
   }
   if (d.stats) {  // partial slots past the grid are zero (the slot contract of include/clskd.h)
-    for (int64_t s = (int64_t)blockIdx.x + gridDim.x; s < a.nblk128; s += gridDim.x)
+    for (int64_t s = (int64_t)blockIdx.x + gridDim.x; s < g.nblk128; s += gridDim.x)
       for (int i = tid; i < d.N * 2; i += 512) d.stats[s * d.N * 2 + i] = 0.0;
   }
-  const int per = (a.ntiles + (int)gridDim.x - 1) / (int)gridDim.x;
+  const int per = (g.ntiles + (int)gridDim.x - 1) / (int)gridDim.x;
   const int tile_begin = blockIdx.x * per;
-  const int ntile_blk = max(0, min(a.ntiles, tile_begin + per) - tile_begin);
+  const int ntile_blk = max(0, min(g.ntiles, tile_begin + per) - tile_begin);
   const unsigned short* wg = reinterpret_cast<const unsigned short*>(d.weight);
   __syncthreads();
 
@@ -202,8 +167,8 @@ __global__ __launch_bounds__(512) void conv_halow_kernel(const HwArgs a) {
   const int HT = __builtin_amdgcn_readfirstlane(kc->HT);
   const int rowstep = __builtin_amdgcn_readfirstlane(kc->sfr * HT);  // halo pixels per tile F-row
   const uint64_t zero_addr = (uint64_t)(uintptr_t)g_hw_zero;
-  const unsigned hlds0 = __builtin_amdgcn_readfirstlane(hw::lds_addr(hbuf));
-  const unsigned wlds0 = __builtin_amdgcn_readfirstlane(hw::lds_addr(wst));
+  const unsigned hlds0 = __builtin_amdgcn_readfirstlane(lds_addr(hbuf));
+  const unsigned wlds0 = __builtin_amdgcn_readfirstlane(lds_addr(wst));
   // halo pixel of (this wave's first row block, time l32); row block i adds rb_pix(i)
   const int pb0 = ((wm * FM) / RBF) * rowstep + ((wm * FM) % RBF) * 32 + l32;
   auto rb_pix = [&](int i) {  // compile-time i: FM row blocks of the wave
@@ -211,33 +176,16 @@ __global__ __launch_bounds__(512) void conv_halow_kernel(const HwArgs a) {
     return (rb / RBF - r0 / RBF) * rowstep + (rb % RBF - r0 % RBF) * 32;
   };
 
-  struct Cur { int b, fb, tb; };
-  auto advance = [&](Cur& c) {
-    if (++c.tb == ntb) {
-      c.tb = 0;
-      if (++c.fb == nfb) { c.fb = 0; ++c.b; }
-    }
-  };
-  auto cur_of = [&](int tile) {
-    Cur c;
-    c.tb = tile % ntb;
-    const int r = tile / ntb;
-    c.fb = r % nfb;
-    c.b = r / nfb;
-    return c;
-  };
   // halo of chunk ch of tile c into halo buffer hb (pieces: this wave's NGH KiB of the buffer;
   // slot = (wave * NGH + i) * 64 + lane, pixel = slot / 4, 16-B chunk = slot % 4)
-  auto issue_halo = [&](const Cur& c, int ch, int hb) -> int {
+  auto issue_halo = [&](const HaloCursor& c, int ch, int hb) -> int {
     const int NGH = __builtin_amdgcn_readfirstlane(kc->NGH);
     const int NPIX = kc->NPIX;
     // pieces past the halo (the last waves' tail) are not issued: the buffer holds
     // ceil(NPIX / 16) KiB, not NW * NGH
     const int nown = max(0, min(NGH, ((NPIX + 15) >> 4) - wave * NGH));
-    const int4 ea = ctA[ch];
-    const int4 eb = ctB[ch];
-    const InT* base = reinterpret_cast<const InT*>(((uint64_t)(unsigned)ea.y << 32) | (unsigned)ea.x) +
-                      (int64_t)c.b * eb.x;
+    const HaloChunk<InT> k = halo_chunk<InT>(ctA, ctB, ch);
+    const InT* base = k.base + (int64_t)c.b * k.sB;
     const int fi_lo = c.fb * FT * kc->sfr + kc->dfmin, ti_lo = c.tb * TT + kc->dtmin;
     const float inv_ht = 1.0f / (float)HT;
     const unsigned dst = hlds0 + hb * halo_bytes;
@@ -247,8 +195,8 @@ __global__ __launch_bounds__(512) void conv_halow_kernel(const HwArgs a) {
       const int hf = (int)(((float)p + 0.5f) * inv_ht);
       const int ht = p - hf * HT;
       const int fi = fi_lo + hf, ti = ti_lo + ht;
-      const bool ok = p < NPIX && (unsigned)fi < (unsigned)eb.y && (unsigned)ti < (unsigned)eb.z;
-      const uint64_t src = ok ? (uint64_t)(uintptr_t)(base + (int64_t)fi * ea.z + (int64_t)ti * ea.w +
+      const bool ok = p < NPIX && (unsigned)fi < (unsigned)k.F && (unsigned)ti < (unsigned)k.T;
+      const uint64_t src = ok ? (uint64_t)(uintptr_t)(base + (int64_t)fi * k.sF + (int64_t)ti * k.sT +
                                                       (((slot & 3) ^ swz(p)) << 3))
                               : zero_addr;
       glds16((const void*)src, dst + (wave * NGH + i) * 1024);
@@ -278,14 +226,14 @@ __global__ __launch_bounds__(512) void conv_halow_kernel(const HwArgs a) {
   const int S = nchunk * NTAPS;        // steps per tile
   const int total = ntile_blk * S;     // steps of this workgroup
   // issue cursors: the halo stream (one chunk ahead) and the weight stream (two steps ahead)
-  Cur hcur = cur_of(tile_begin);
+  HaloCursor hcur = halo_cursor_of(tile_begin, nfb, ntb);
   int h_ch = 0, h_left = ntile_blk * nchunk, h_buf = 0;
   auto issue_next_halo = [&]() -> int {
     if (h_left <= 0) return 0;
     const int n = issue_halo(hcur, h_ch, h_buf);
     h_buf ^= 1;
     --h_left;
-    if (++h_ch == nchunk) { h_ch = 0; advance(hcur); }
+    if (++h_ch == nchunk) { h_ch = 0; hcur.advance(nfb, ntb); }
     return n;
   };
   int w_ch = 0, w_t = 0, w_issued = 0;
@@ -304,7 +252,7 @@ __global__ __launch_bounds__(512) void conv_halow_kernel(const HwArgs a) {
   }
   raw_barrier();
 
-  Cur cur = cur_of(tile_begin);
+  HaloCursor cur = halo_cursor_of(tile_begin, nfb, ntb);
   int gs = 0;
   int hprev = 0;  // halo pieces issued in the previous step (after its slab)
   for (int ti = 0; ti < ntile_blk; ++ti) {
@@ -421,7 +369,7 @@ __global__ __launch_bounds__(512) void conv_halow_kernel(const HwArgs a) {
       }
       raw_barrier();  // staging reads done before the next step's halo DMA reuses the buffer
     }
-    advance(cur);
+    cur.advance(nfb, ntb);
   }
 
   if (d.stats || a.f.acc) {  // workgroup partial: lane halves and row-block waves in a fixed order
@@ -448,7 +396,7 @@ __global__ __launch_bounds__(512) void conv_halow_kernel(const HwArgs a) {
           Qx += red[(w * BN + n) * 2 + 1];
         }
       }, reinterpret_cast<int*>(red + WM * BN * 2), blockIdx.x, gridDim.x);
-    } else if (blockIdx.x < a.nblk128) {
+    } else if (blockIdx.x < g.nblk128) {
       for (int n = tid; n < d.N; n += 512) {
         double Sx = 0.0, Qx = 0.0;
         for (int w = 0; w < WM; ++w) {
@@ -465,66 +413,29 @@ __global__ __launch_bounds__(512) void conv_halow_kernel(const HwArgs a) {
 // Plan + eligibility (host).  Returns false (conv_gemm8 path) when the layer does not fit.
 static bool halow_plan(const clskd_conv_desc& d, HwArgs& a, size_t& lds, int& tt, int& bn) {
   using namespace hw;
-  if (!is_lowp(d.in_dtype) || d.N <= 64 || d.N > 256 || d.ntaps < 3 || d.ntaps > 16 ||
-      d.stride_t != 1 || d.accumulate)
+  if (!is_lowp(d.in_dtype) || d.N <= 64 || d.N > 256 || d.ntaps < 3 || d.stride_t != 1 || d.accumulate)
     return false;
   if (d.stride_f < 1 || d.stride_f > 2 || d.ctot < CW || d.Fo < 4) return false;
   if (d.out_dtype != CLSKD_F32 && d.out_dtype != d.in_dtype) return false;
   a.d = d;
-  int nch = 0, kofs = 0;
-  for (int s = 0; s < d.nseg; ++s) {
-    if (d.seg_c[s] % CW) return false;
-    for (int c0 = 0; c0 < d.seg_c[s]; c0 += CW) {
-      if (nch >= MAXCH) return false;
-      a.chunk_seg[nch] = s;
-      a.chunk_c0[nch] = c0;
-      a.chunk_kofs[nch] = kofs + c0;
-      ++nch;
-    }
-    kofs += d.seg_c[s];
-  }
-  if (kofs != d.ctot || d.ntaps * d.ctot != d.K) return false;
-  a.nchunk = nch;
-  int dfmin = 1 << 20, dfmax = -(1 << 20), dtmin = 1 << 20, dtmax = -(1 << 20);
-  for (int t = 0; t < d.ntaps; ++t) {
-    dfmin = d.tap_df[t] < dfmin ? d.tap_df[t] : dfmin;
-    dfmax = d.tap_df[t] > dfmax ? d.tap_df[t] : dfmax;
-    dtmin = d.tap_dt[t] < dtmin ? d.tap_dt[t] : dtmin;
-    dtmax = d.tap_dt[t] > dtmax ? d.tap_dt[t] : dtmax;
-  }
   tt = d.Fo >= 8 ? 32 : 64;  // 8 x 32 tiles; 4 x 64 when the layer has 4..7 F-rows
-  const int FT = 256 / tt;
   bn = d.N <= 128 ? 128 : 256;
-  a.dfmin = dfmin;
-  a.dtmin = dtmin;
-  a.HF = (FT - 1) * d.stride_f + (dfmax - dfmin + 1);
   // halo rows padded so one F-row of the tile is a multiple of 16 pixels (rowstep = stride_f *
   // HT): every row block's pixel then has the same 16-B chunk swizzle as the wave's first one,
   // and its fragment address is the first one's plus a uniform offset (the padding pixels are
   // loaded, never read)
   const int hpad = d.stride_f == 2 ? 8 : 16;
-  a.HT = (int)cdiv((tt - 1) + (dtmax - dtmin + 1), hpad) * hpad;
-  if (a.HF > 255 || a.HT > 255) return false;
-  a.NPIX = a.HF * a.HT;
-  for (int t = 0; t < 16; ++t) {
-    a.tap_pix[t] = t < d.ntaps ? (d.tap_df[t] - dfmin) * a.HT + (d.tap_dt[t] - dtmin) : 0;
-  }
-  a.NGH = (int)cdiv((int64_t)a.NPIX * 4, 64 * NW);  // 4 x 16-B slots per pixel
+  if (!halo_geom_plan(d, CW, 256 / tt, tt, hpad, 4, a.g) || a.g.nchunk > MAXCH) return false;
+  if (d.ntaps * d.ctot != d.K) return false;
+  halo_tap_pix(d, a.g, a.tap_pix);
+  a.NGH = (int)cdiv((int64_t)a.g.NPIX * 4, 64 * NW);  // 4 x 16-B slots per pixel
   if (a.NGH > MAXG) return false;
-  a.halo_bytes = (int)cdiv(a.NPIX, 16) * 1024;  // whole 1-KiB pieces of 16 pixels
+  a.halo_bytes = (int)cdiv(a.g.NPIX, 16) * 1024;  // whole 1-KiB pieces of 16 pixels
   lds = 2 * (size_t)a.halo_bytes + (size_t)BST * bn * 64 + 2 * MAXCH * 16 + 16 * 4 +
         sizeof(HwConsts) + (size_t)bn * (4 + 8);
-  for (int s = 0; s < d.nseg; ++s)
-    if (d.seg[s].sB > INT32_MAX || d.seg[s].sF > INT32_MAX || d.seg[s].sT > INT32_MAX) return false;
   if ((int64_t)d.N * d.K >= ((int64_t)1 << 31)) return false;
   if (lds > 160 * 1024) return false;
   if ((d.stats || d.bn_fold) && (size_t)2 * bn * 16 + 16 > 2 * (size_t)a.halo_bytes) return false;
-  a.nfb = (int)cdiv(d.Fo, FT);
-  a.ntb = (int)cdiv(d.To, tt);
-  const int64_t nt = (int64_t)d.B * a.nfb * a.ntb;
-  if (nt < 4 || nt > (1 << 30)) return false;
-  a.ntiles = (int)nt;
-  a.nblk128 = (int)cdiv((int64_t)d.B * d.Fo * d.To, 128);
   a.f = make_bnfold(d);
   const int ch16 = d.out_dtype == CLSKD_F32 ? 4 : 8;
   a.vec = d.oNlo == 1 && d.nlo >= d.N && d.N % ch16 == 0 && (((uintptr_t)d.out) & 15) == 0 &&
@@ -535,35 +446,33 @@ static bool halow_plan(const clskd_conv_desc& d, HwArgs& a, size_t& lds, int& tt
   return true;
 }
 
-// Whether launch_conv_halow would take the layer (CLSKD_HALOW=1; default 0 keeps the wide
-// layers on conv_gemm8 — A/B switch).
-bool conv_halow_takes(const clskd_conv_desc& d) {
+// Every condition under which the layer is not this kernel's (conv_gemm8 runs it): the knob
+// (CLSKD_HALOW=1; default 0 keeps the wide layers on conv_gemm8 — A/B switch), the plan, a built
+// tap count.  (The grid is cut to the statistics slots at the launch: no statistics condition.)
+static bool halow_decide(const clskd_conv_desc& d, HwArgs& a, size_t& lds, int& tt, int& bn) {
   if (knob(KNOB_HALOW) == 0) return false;
+  if (!halow_plan(d, a, lds, tt, bn)) return false;
+  return d.ntaps == 4 || d.ntaps == 6 || d.ntaps == 9 || d.ntaps == 10;
+}
+
+// Whether launch_conv_halow would take the layer (the same decision, nothing launched).
+bool conv_halow_takes(const clskd_conv_desc& d) {
   HwArgs a;
   size_t lds = 0;
   int tt = 0, bn = 0;
-  if (!halow_plan(d, a, lds, tt, bn)) return false;
-  switch (d.ntaps) {
-    case 4: case 6: case 9: case 10: return true;
-    default: return false;
-  }
+  return halow_decide(d, a, lds, tt, bn);
 }
 
 int launch_conv_halow(const clskd_conv_desc& d, hipStream_t st, bool* launched) {
-  *launched = false;
-  if (knob(KNOB_HALOW) == 0) return CLSKD_OK;
   HwArgs a;
   size_t lds = 0;
   int tt = 0, bn = 0;
-  if (!halow_plan(d, a, lds, tt, bn)) return CLSKD_OK;
-  static int ncu = [] {
-    int v = 256;
-    (void)hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, 0);
-    return v > 0 ? v : 256;
-  }();
+  *launched = halow_decide(d, a, lds, tt, bn);
+  if (!*launched) return CLSKD_OK;
+  const int ncu = device_cu_count();
   // persistent grid; with partial statistics slots (one per workgroup) at most ceil(M/128)
-  int grid = a.ntiles < ncu ? a.ntiles : ncu;
-  if (d.stats && grid > a.nblk128) grid = a.nblk128;
+  int grid = a.g.ntiles < ncu ? a.g.ntiles : ncu;
+  if (d.stats && grid > a.g.nblk128) grid = a.g.nblk128;
   const bool f32out = d.out_dtype == CLSKD_F32;
 #define HW_LAUNCH(BN_, WM_, TT_, O_, NT_, I_)                                                   \
   do {                                                                                          \
@@ -591,18 +500,16 @@ int launch_conv_halow(const clskd_conv_desc& d, hipStream_t st, bool* launched) 
   do {                                                                                          \
     if (d.in_dtype == CLSKD_F16) HW_NI(NT_, _Float16); else HW_NI(NT_, __bf16);                 \
   } while (0)
-  switch (d.ntaps) {
+  switch (d.ntaps) {  // (halow_decide: one of these)
     case 4: HW_NT(4); break;
     case 6: HW_NT(6); break;
     case 9: HW_NT(9); break;
-    case 10: HW_NT(10); break;
-    default: return CLSKD_OK;  // not a built tap count: conv_gemm8
+    default: HW_NT(10); break;
   }
 #undef HW_NT
 #undef HW_NI
 #undef HW_TT
 #undef HW_LAUNCH
-  *launched = true;
   return CLSKD_OK;
 }
 

@@ -35,25 +35,12 @@ namespace clskd {
 
 namespace sp3 {
 typedef short s16x8 __attribute__((ext_vector_type(8)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
 
 // 16-B chunk swizzle of a plane row (BK bf16 k's = BK / 8 chunks): conflict-free 16-lane
 // fragment reads (BK 16: rows of 32 B, 8 rows cover the 64 banks; BK 32: rows of 64 B, 4 rows)
 template <int BK>
 __device__ __forceinline__ int swz(int row) {
   return BK == 16 ? (row >> 3) & 1 : BK == 32 ? (row >> 2) & 3 : (row >> 1) & 7;
-}
-
-// hi / lo bf16 split of 4 fp32 values (RNE both)
-__device__ __forceinline__ void split4(const f32x4 v, s16x4& hi, s16x4& lo) {
-  bf16x4 h, l;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    h[i] = (__bf16)v[i];
-    l[i] = (__bf16)(v[i] - (float)h[i]);
-  }
-  hi = __builtin_bit_cast(s16x4, h);
-  lo = __builtin_bit_cast(s16x4, l);
 }
 
 template <typename T>
@@ -460,11 +447,7 @@ static bool split_plan(const clskd_conv_desc& d, SplitArgs& a, int& nt, int& bk,
     a.kt_cpt = d.ctot / bk;
   }
   a.f = make_bnfold(d);
-  static int ncu = [] {
-    int v = 256;
-    (void)hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, 0);
-    return v > 0 ? v : 256;
-  }();
+  const int ncu = device_cu_count();
   // 4-wave workgroups, as many per CU as LDS holds (up to three): more waves per SIMD hide more
   // of the gather latency
   const size_t tab = (size_t)2 * 128 * (16 + 16 + 8);

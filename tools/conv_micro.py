@@ -9,6 +9,9 @@ conv_split3_kernel and on conv_halo_split3_kernel (CLSKD_HALO_SPLIT=0 / 1) inter
 process; per route the minimum and the spread of --rounds repetitions of --iters launches.
 
     python tools/conv_micro.py --student --iters 20 --rounds 3 [--only enc3,dec2p0]
+
+--student --fp32: the same shapes as plain fp32 descriptors (precision='fp32': conv_halo_f32_kernel
+where it takes the layer, else conv_igemm_f32); minimum and spread of the repetitions.
 """
 import argparse
 import os
@@ -106,7 +109,7 @@ STUDENT = {
 }
 
 
-def make_student(segc, co, kind, fi, dev):
+def make_student(segc, co, kind, fi, dev, split=True):
     g = torch.Generator(device="cpu").manual_seed(0)
     segs = [ops.seg_bftc((torch.randn(B, fi, T, c, generator=g) * 0.5).to(dev)) for c in segc]
     if kind == "enc":
@@ -124,7 +127,7 @@ def make_student(segc, co, kind, fi, dev):
     st = torch.empty(ops.conv_mblocks(B, Fo, T) * co * 2, device=dev, dtype=torch.float64)
 
     def run():
-        with ops.split_products(True):
+        with ops.split_products(split):
             ops.conv(segs, taps, B, Fo, T, co, wp, bias, out, omap, stride_f=sf, stats=st,
                      mfma_only=True)
     return run, (B * Fo * T, co, K)
@@ -135,6 +138,23 @@ def student(a, dev, names):
     split-product launches: the two routes interleaved in this one process, `rounds` repetitions of
     `iters` back-to-back launches each; minimum and spread (max - min) of the repetitions."""
     from clskd import _lib
+    if a.fp32:  # plain fp32 descriptors: one route
+        for name in names:
+            run, (M, N, K) = make_student(*STUDENT[name], dev=dev, split=False)
+            t = []
+            for r in range(a.rounds):
+                for _ in range(2):
+                    run()
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for _ in range(a.iters):
+                    run()
+                e1.record()
+                torch.cuda.synchronize()
+                t.append(e0.elapsed_time(e1) * 1e3 / a.iters)
+            print(f"{name:7s} M={M:7d} N={N:3d} K={K:4d}  fp32 min {min(t):6.1f} spread {max(t) - min(t):4.1f} us "
+                  f"[{ops.conv_kernel_of_last_launch()}]", flush=True)
+        return
     try:
         default = _lib.set_knob("CLSKD_HALO_SPLIT", 1)
         routes = (0, 1)
@@ -169,6 +189,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--student", action="store_true",
                     help="the student's split-product launches: split3 against halo_split")
+    ap.add_argument("--fp32", action="store_true",
+                    help="with --student: plain fp32 descriptors (conv_halo_f32_kernel's layers)")
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--only", default="")
     ap.add_argument("--ab", default="", help="KNOB=v1,v2: interleaved A/B of a dispatch knob")
