@@ -656,6 +656,41 @@ int clskd_stft_mag_loss_bwd(const float* X, const float* Y, int64_t rows, int32_
 int clskd_complex_combine_bwd(const float* dreal, const float* dimag, int32_t B, int64_t n,
                               float* dh, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Backward of the asteroid DCCRNet_mini training step (csrc/mini_bwd.hip; the rest of that
+ * backward runs on the entries above).
+ * clskd_mask_bdt_bwd: reverse of clskd_mask_bdt (asteroid complex_nn.BoundComplexMask('tanh')
+ *   then DCCRNet.apply_masks, oracle/asteroid_cpu.py:127-131).  dest = dL/d est [B][T][ldest]
+ *   (re at f, im at 257 + f; the Nyquist columns 256 / 513 and the tail are ignored), spec as
+ *   the forward's; dmask [B][256][Tm][2] receives, with M = mr + i mi, r = |M|, s = tanh r,
+ *   u = M / r and g = conj(X) dest:  (1 - s^2)(u.g) u + (s / r)(g - (u.g) u);  g itself at r = 0
+ *   (the limit of the Jacobian; the forward yields 0 there).  Columns T <= tm < Tm get zero.
+ *   1 <= B <= 65535, 1 <= T <= Tm, ldspec, ldest >= 514.
+ * clskd_bn_bwd_reim: clskd_bn_bwd for asteroid's OnReIm(BatchNorm2d) + OnReIm(PReLU) pair
+ *   (oracle/asteroid_cpu.py:96-97, 120-121; forward clskd_bn_apply_reim) over fp32 BFTC
+ *   x [rows][C]: slope alpha_re_im[0] on channels [0, C/2), alpha_re_im[1] on [C/2, C);
+ *   dalpha_re_im[2] (optional) receives the two slope gradients, each a fixed-order fp64 sum over
+ *   its half.  C a multiple of 4; work / nblk as clskd_bn_bwd (clskd_bn_bwd_workspace /
+ *   clskd_bn_bwd_blocks); x, dy, dx, scale, shift, work 16-byte aligned.
+ * clskd_mse_loss_grad: F.mse_loss(a, b, reduction='mean') (distill_MSE.py:85) and its gradient
+ *   in one pass over two fp32 arrays of n elements: loss_out[0] (+)= scale * mean((a - b)^2)
+ *   (fp64 block partials combined in a fixed order: bitwise repeatable), da (+)= scale * 2 (a - b)
+ *   / n (optional).  `accumulate` covers both.  work: clskd_mse_loss_grad_workspace(n) doubles.
+ *   16-byte accesses when a, b and da are 16-byte aligned, scalar otherwise and for n % 4.
+ * -------------------------------------------------------------------------------------- */
+int clskd_mask_bdt_bwd(const float* spec, int32_t ldspec, const float* mask, int32_t Tm,
+                       int32_t B, int32_t T, const float* dest, int32_t ldest, float* dmask,
+                       void* stream);
+int clskd_bn_bwd_reim(const float* x, const float* dy, int64_t rows, int32_t C,
+                      const float* scale, const float* shift, const float* mean,
+                      const float* var, float eps, const float* gamma, const float* alpha_re_im,
+                      double* work, int32_t nblk, float* dgamma, float* dbeta,
+                      float* dalpha_re_im, float* dx, int32_t accumulate_dx,
+                      int32_t accumulate_params, void* stream);
+int64_t clskd_mse_loss_grad_workspace(int64_t n);
+int clskd_mse_loss_grad(const float* a, const float* b, int64_t n, float scale, double* work,
+                        float* loss_out, float* da, int32_t accumulate, void* stream);
+
 /* LSTM backward through time (nn.LSTM, tools_for_model.py:159-174).  pre: the forward's gate
  * pre-activations [nws][nseq][T][4H] (strided like gx; rebuild them as gx + h_{t-1} W_hh^T with
  * one accumulate conv over the saved h history), dh: dL/dh_t, whh [nws][4H][H].  Writes the

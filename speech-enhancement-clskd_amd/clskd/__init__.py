@@ -8,6 +8,8 @@ Drop-in counterparts of the reference modules (KhanhNguyen4999/Speech-Enhancemen
   tools_for_loss.py       -> clskd.tools_for_loss.si_snr
   distill.py              -> clskd.distill.KnowledgeDistillation (training_step)
   distill_SPKD.py         -> clskd.distill.SPKDDistillation
+  distill_SPKD.py / distill_MSE.py / distill_STFT.py with the asteroid DCCRNet_mini student
+                          -> clskd.distill_mini.OutputDistillation (kd="spkd" | "mse" | "stft")
   config.py               -> clskd.config
 A whole step can be captured and replayed as one hipGraph (clskd.graph.StepGraph).
 All arithmetic runs in libclskd_hip.so (gfx950); there is no CPU fallback.
@@ -24,6 +26,12 @@ def __getattr__(name):
     if name in ("KnowledgeDistillation", "SPKDDistillation", "clskd_step"):
         from . import distill
         return getattr(distill, name)
+    if name == "OutputDistillation":
+        from .distill_mini import OutputDistillation
+        return OutputDistillation
+    if name == "DCCRNet_mini":
+        from .asteroid import DCCRNet_mini
+        return DCCRNet_mini
     if name in ("MultiResolutionSTFTLoss", "SPKDLoss", "build_review_kd", "ReviewKD", "ABF"):
         from . import framework
         return getattr(framework, name)

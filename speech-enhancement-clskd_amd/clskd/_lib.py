@@ -232,6 +232,11 @@ SIGNATURES = {
     "clskd_frame_pad_bwd": (_i32, [_p, _i32, _i32, _i32, _i32, _i32, _p, _i64, _i32, _p]),
     "clskd_stft_mag_loss_bwd": (_i32, [_p, _p, _i64, _i32, _i32, _f32, _p, _i32, _p]),
     "clskd_complex_combine_bwd": (_i32, [_p, _p, _i32, _i64, _p, _p]),
+    "clskd_mask_bdt_bwd": (_i32, [_p, _i32, _p, _i32, _i32, _i32, _p, _i32, _p, _p]),
+    "clskd_bn_bwd_reim": (_i32, [_p, _p, _i64, _i32, _p, _p, _p, _p, _f32, _p, _p, _p, _i32, _p,
+                                 _p, _p, _p, _i32, _i32, _p]),
+    "clskd_mse_loss_grad_workspace": (_i64, [_i64]),
+    "clskd_mse_loss_grad": (_i32, [_p, _p, _i64, _f32, _p, _p, _p, _i32, _p]),
     "clskd_lstm_bwd": (_i32, [_p, _i64, _i64, _i64, _p, _i64, _i64, _i64, _p, _i32, _i32, _i32,
                               _i32, _p, _i32, _p, _i64, _i64, _i64, _p]),
     "clskd_spkd_grad_ranges": (_i32, [C.POINTER(C.c_void_p), C.POINTER(C.c_int32),

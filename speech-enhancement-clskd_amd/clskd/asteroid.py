@@ -251,16 +251,21 @@ class DCCRNet_mini(nn.Module):
         return self._packed(("fb",), (ef, df), build)
 
     # ------------------------------------------------------------------ BatchNorm + PReLU
-    def _bn_prelu(self, raw, norm, act, train, part, nblk):
+    def _bn_prelu(self, raw, norm, act, train, part, nblk, tape=None, key=None):
         """OnReIm(BatchNorm2d) + OnReIm(PReLU) over BFTC [.., re | im] channels in place; the
-        re / im modules' running statistics are updated as asteroid's train mode does."""
+        re / im modules' running statistics are updated as asteroid's train mode does.  With a
+        tape the raw output is kept (the same arithmetic, out of place) and tape[key] receives
+        (raw, [scale | shift], [mean; var], norm, act, gamma [re | im], alpha [re, im]) for
+        asteroid_backward.mini_backward."""
         C2 = raw.shape[-1]
         nr, ni = norm.re_module, norm.im_module
         g = torch.cat([nr.weight, ni.weight]).float().contiguous()
         b = torch.cat([nr.bias, ni.bias]).float().contiguous()
         rm = torch.cat([nr.running_mean, ni.running_mean]).float().contiguous()
         rv = torch.cat([nr.running_var, ni.running_var]).float().contiguous()
+        mv = torch.empty(2, C2, device=raw.device, dtype=torch.float32) if tape is not None else None
         coef = ops.batch_norm_bftc(raw, None, g, b, rm, rv, train, nr.momentum, nr.eps, 1,
+                                   stats_out=(mv[0], mv[1]) if mv is not None else None,
                                    partial=(part, nblk) if train else None)
         if train:
             with torch.no_grad():
@@ -273,10 +278,13 @@ class DCCRNet_mini(nn.Module):
         alpha = torch.cat([act.re_module.weight, act.im_module.weight]).float().contiguous()
         rows = raw.numel() // C2
         sc = coef.data_ptr()
-        check(ops.lib().clskd_bn_apply_reim(ptr(raw), ptr(raw), rows, C2, sc, sc + 4 * C2,
+        out = raw if tape is None else torch.empty_like(raw)
+        check(ops.lib().clskd_bn_apply_reim(ptr(raw), ptr(out), rows, C2, sc, sc + 4 * C2,
                                             ptr(alpha), ops._dt(raw), ops._stream()),
               "bn_apply_reim")
-        return raw
+        if tape is not None:
+            tape.setdefault(key, []).append((raw, coef, mv, norm, act, g, alpha))
+        return out
 
     # ------------------------------------------------------------------ forward
     def forward(self, wav):
@@ -287,9 +295,15 @@ class DCCRNet_mini(nn.Module):
             x = x.unsqueeze(0)
         return self.run(x, self.training)["wav"].unsqueeze(1)
 
-    def run(self, x, train=True):
+    def run(self, x, train=True, tape=None):
+        """tape: a dict that receives what asteroid_backward.mini_backward needs — the spectrum,
+        every block's raw conv output with its BatchNorm coefficients and batch statistics, the
+        encoder / decoder outputs, the LSTM gate pre-activations, cell states and h histories,
+        the mask.  Outputs and running statistics are bitwise those of a run without one."""
         if not x.is_cuda:
             raise RuntimeError("clskd DCCRNet_mini runs on the HIP device (no CPU fallback)")
+        if tape is not None and not train:
+            raise ValueError("DCCRNet_mini.run: a tape needs train=True (batch statistics)")
         x = x.float().contiguous()
         B, L = x.shape
         if L < 400:
@@ -315,7 +329,7 @@ class DCCRNet_mini(nn.Module):
             ops.conv([seg_bftc(cur)], [(kf - 2, kt) for kf in range(5) for kt in range(2)], B, Fo,
                      To, Co, self._enc_w(i), None, raw, OutMap(Fo * To * Co, To * Co, Co),
                      stride_f=2, stats=part)
-            cur = self._bn_prelu(raw, blk.norm, blk.activation, train, part, nmb)
+            cur = self._bn_prelu(raw, blk.norm, blk.activation, train, part, nmb, tape, "enc_bn")
             enc.append(cur)
             F, Ti = Fo, To
         # ---- DCCRMaskNetRNN_mini: two complex LSTM layers (batch-first) + complex Linear
@@ -336,8 +350,20 @@ class DCCRNet_mini(nn.Module):
                 ops.conv(segs, taps, B, 1, Ti, 8 * H, wp, bias, gx[half],
                          OutMap(Ti * 8 * H, 0, 8 * H))
             hs = torch.empty(2, 2 * B, Ti, H, **f32)
-            ops.lstm_recurrent(gx, 4 * H, Ti * 8 * H, 8 * H, whh, 2, 2 * B, Ti, H, hs,
-                               2 * B * Ti * H, Ti * H, H)
+            # taped: the recurrence leaves the gate pre-activations in gx (lstm_bwd's `pre`) and
+            # the cell states in `cells`
+            pre = tape is not None and ops.lstm_pre_capable(H)
+            cells = None
+            if pre:
+                cells = torch.empty(2 * 2 * B * Ti * H, **f32)
+                ops.lstm_recurrent_pre(gx, 4 * H, Ti * 8 * H, 8 * H, whh, 2, 2 * B, Ti, H, hs,
+                                       2 * B * Ti * H, Ti * H, H, cbuf=cells)
+            else:
+                ops.lstm_recurrent(gx, 4 * H, Ti * 8 * H, 8 * H, whh, 2, 2 * B, Ti, H, hs,
+                                   2 * B * Ti * H, Ti * H, H)
+            if tape is not None:
+                tape.setdefault("lstm", []).append(dict(gx=gx, hs=hs, r_in=r_in, pre=pre,
+                                                        cells=cells))
             ro = torch.empty(B, Ti, H, **f32)
             io = torch.empty(B, Ti, H, **f32)
             ops.complex_combine(hs[0, :B], hs[1, B:], hs[0, B:], hs[1, :B], ro, io)
@@ -369,9 +395,15 @@ class DCCRNet_mini(nn.Module):
                          OutMap(2 * F * (Ti + 1) * Co, (Ti + 1) * Co, Co, of_mul=2, of_add=parity),
                          stats=part, stats_offset=parity * nmb * Co * 2)
             if not is_out:
-                raw = self._bn_prelu(raw, mod.norm, mod.activation, train, part, 2 * nmb)
+                raw = self._bn_prelu(raw, mod.norm, mod.activation, train, part, 2 * nmb, tape,
+                                     "dec_bn")
+                if tape is not None:
+                    tape.setdefault("dec", []).append(raw)
             prev, F, Ti = raw, 2 * F, Ti + 1
         mask = prev  # [B][256][T][2]
+        if tape is not None:
+            tape.update(B=B, T=T, L=L, spec=spec, xin=xin, enc=enc, r_out=r_in, rnn_out=rnn_out,
+                        mask=mask)
         # ---- BoundComplexMask('tanh') * spectrum, Nyquist 0; STFTFB synthesis; pad to L
         est = torch.empty(B, T, 516, **f32)
         check(ops.lib().clskd_mask_bdt(ptr(spec), 514, ptr(mask), T, B, T, ptr(est), 516,

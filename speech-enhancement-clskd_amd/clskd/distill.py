@@ -139,6 +139,7 @@ def _validation_step(module, batch):
     of si_sdr, stoi and their improvements — the dict the reference passes to self.log_dict.
     All metrics run on the device (clskd.metrics); returned as Python floats."""
     from . import metrics
+    from .asteroid import DCCRNet_mini
     x, y = batch
     x = x.float().reshape(x.shape[0], -1).contiguous()
     y = y.float().reshape(x.shape[0], -1).contiguous()
@@ -147,7 +148,10 @@ def _validation_step(module, batch):
     student.eval()
     try:
         with torch.no_grad():
-            est = student(x, is_feat=True)
+            if isinstance(student, DCCRNet_mini):  # distill_mini.OutputDistillation: [B, 1, L]
+                est = student(x).reshape(x.shape)
+            else:
+                est = student(x, is_feat=True)
             utt = metrics.get_metrics(x, y, est, sample_rate=module.cfg.fs)
             res = metrics.summarize(utt)
     finally:

@@ -1514,6 +1514,44 @@ def complex_combine_bwd(dre, dim, dh):
                                           _stream()), "complex_combine_bwd")
 
 
+def mask_bdt_bwd(spec, mask, T, dest, dmask):
+    """Reverse of clskd_mask_bdt: dest [B][T][ldest] -> dmask like mask [B][256][Tm][2]."""
+    B = spec.shape[0]
+    check(lib().clskd_mask_bdt_bwd(ptr(spec), spec.shape[-1], ptr(mask), mask.shape[2], B, T,
+                                   ptr(dest), dest.shape[-1], ptr(dmask), _stream()),
+          "mask_bdt_bwd")
+    return dmask
+
+
+def bn_bwd_reim(x, dy, scale, shift, mean, var, eps, gamma, alpha, dx, dgamma=None, dbeta=None,
+                dalpha=None, accumulate_dx=False, accumulate_params=False):
+    """bn_bwd for asteroid's OnReIm(BatchNorm2d) + OnReIm(PReLU) over fp32 BFTC x: alpha [2]
+    (slope of the real half, of the imaginary half), dalpha [2]."""
+    L = lib()
+    Cn = x.shape[-1]
+    rows = x.numel() // Cn
+    assert x.dtype == torch.float32 and alpha.numel() == 2
+    nblk = int(L.clskd_bn_bwd_blocks(rows, Cn))
+    work = torch.empty(int(L.clskd_bn_bwd_workspace(nblk, Cn)), dtype=torch.float64, device=x.device)
+    check(L.clskd_bn_bwd_reim(ptr(x), ptr(dy), rows, Cn, ptr(scale), ptr(shift), ptr(mean),
+                              ptr(var), eps, ptr(gamma), ptr(alpha), ptr(work), nblk, ptr(dgamma),
+                              ptr(dbeta), ptr(dalpha), ptr(dx), int(accumulate_dx),
+                              int(accumulate_params), _stream()), "bn_bwd_reim")
+    return dx
+
+
+def mse_loss_grad(a, b, loss_out, da=None, scale=1.0, accumulate=False):
+    """loss_out[0] (+)= scale * mean((a - b)^2); da (+)= scale * 2 (a - b) / n (fp32, contiguous)."""
+    n = a.numel()
+    assert b.numel() == n and a.dtype == b.dtype == torch.float32
+    assert a.is_contiguous() and b.is_contiguous() and (da is None or da.is_contiguous())
+    L = lib()
+    work = torch.empty(int(L.clskd_mse_loss_grad_workspace(n)), dtype=torch.float64, device=a.device)
+    check(L.clskd_mse_loss_grad(ptr(a), ptr(b), n, scale, ptr(work), ptr(loss_out), ptr(da),
+                                int(accumulate), _stream()), "mse_loss_grad")
+    return loss_out
+
+
 def lstm_bwd(pre, p_strides, dh, d_strides, whh, nws, nseq, T, H, dgates, g_strides, cells=None):
     """cells: the forward's cell states (lstm_recurrent_pre's cbuf), else recomputed here."""
     c_ready = cells is not None
