@@ -691,6 +691,53 @@ int64_t clskd_mse_loss_grad_workspace(int64_t n);
 int clskd_mse_loss_grad(const float* a, const float* b, int64_t n, float scale, double* work,
                         float* loss_out, float* da, int32_t accumulate, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Supervised losses of DCCRN.loss (DCCRN.py:259-411) with gradients (csrc/sup_loss.hip).  No
+ * entry allocates or synchronises; reductions are fp64 block partials summed in a fixed order by
+ * a finalize launch (bitwise repeatable).
+ * clskd_wave_loss: s (estimate) and y (labels) [B][L] fp32 with row strides lds / ldy (any
+ *   alignment of the rows).  One pass gives per row sum s^2, sum y^2, sum s y and sum (s - y)^2
+ *   (accumulated from the differences); the finalize writes out6[1..5] =
+ *     l0 = F.mse_loss(s, y)             l1 = -sdr(y, s)       l2 = -si_snr(s, y)
+ *     l3 = -si_sdr(y, s)                l4 = -si_sdr(s, y)    (tools_for_loss.py:30-97)
+ *   and out6[0] = sum_k w5[k] l_k over the non-zero weights (w5: 5 host floats), and, when coef
+ *   is given, coef[B][2] = upstream * (p_b, p_b + q_b) with d out6[0] / d s_b = p_b s_b + q_b y_b
+ *   (the second column is the sum so that the gradient pass can form p (s - y) + (p + q) y, which
+ *   keeps its digits when s ~ y).
+ *   work: clskd_wave_loss_workspace(B, L) doubles, 8-byte aligned.
+ * clskd_wave_loss_grad: d_wav[b] (+)= coef[b][0] (s_b - y_b) + coef[b][1] y_b (row stride ldd).
+ * clskd_mel_loss: get_array_mel_loss (tools_for_loss.py:195-252) of the magnitudes
+ *   sqrt(re^2 + im^2 + 1e-7) of two frame-major spectra [B][T][ld >= 514] (re at f, im at 257 + f).
+ *   Rows are the reference's x.view(-1, 257) of each clip's contiguous [257][T] magnitudes: row r
+ *   = flat elements [257 r, 257 r + 257) with flat n = f T + t.  out2[0] (+)= scale * loss,
+ *   out2[1] = loss.  work: clskd_mel_loss_workspace(B, T) doubles.  table: CLSKD_MEL_TABLE_WORDS
+ *   4-byte words on the device, built once by the host from melFilterBank(16 | 32 | 64, 512)
+ *   (filters 0..15, 16..47, 48..111):
+ *     float  W[112][257]      dense filters
+ *     int32  supp[112][2]     [first, last + 1) non-zero position of each filter
+ *     int32  pk[257][6]       per position the (<= 2 per scale) filters covering it, 0 padded
+ *     float  pw[257][6]       their weights, 0 padded
+ * clskd_mel_loss_bwd: d_est [B][T][ldd >= 514] (+)= upstream * d loss / d est (columns >= 514
+ *   untouched); recomputes the projections, stores nothing per row.
+ * -------------------------------------------------------------------------------------- */
+#define CLSKD_MEL_FILTERS 112
+#define CLSKD_MEL_TABLE_WORDS (112 * 257 + 112 * 2 + 257 * 6 + 257 * 6)
+#define CLSKD_MEL_MAX_T (1 << 22)
+int64_t clskd_wave_loss_workspace(int32_t B, int32_t L);
+int clskd_wave_loss(const float* s, int64_t lds, const float* y, int64_t ldy, int32_t B, int32_t L,
+                    const float* w5, float upstream, double* work, float* out6, float* coef,
+                    void* stream);
+int clskd_wave_loss_grad(const float* s, int64_t lds, const float* y, int64_t ldy, int32_t B,
+                         int32_t L, const float* coef, float* d_wav, int64_t ldd,
+                         int32_t accumulate, void* stream);
+int64_t clskd_mel_loss_workspace(int32_t B, int32_t T);
+int clskd_mel_loss(const float* clean, int32_t ldc, const float* est, int32_t lde, int32_t B,
+                   int32_t T, const void* table, double* work, float scale, int32_t accumulate,
+                   float* out2, void* stream);
+int clskd_mel_loss_bwd(const float* clean, int32_t ldc, const float* est, int32_t lde, int32_t B,
+                       int32_t T, const void* table, float upstream, float* d_est, int32_t ldd,
+                       int32_t accumulate, void* stream);
+
 /* LSTM backward through time (nn.LSTM, tools_for_model.py:159-174).  pre: the forward's gate
  * pre-activations [nws][nseq][T][4H] (strided like gx; rebuild them as gx + h_{t-1} W_hh^T with
  * one accumulate conv over the saved h history), dh: dL/dh_t, whh [nws][4H][H].  Writes the

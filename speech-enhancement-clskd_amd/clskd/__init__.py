@@ -5,7 +5,10 @@ Drop-in counterparts of the reference modules (KhanhNguyen4999/Speech-Enhancemen
   framework.py            -> clskd.framework (MultiResolutionSTFTLoss, SPKDLoss, ABF, ReviewKD,
                              build_review_kd)
   feature_extraction.py   -> clskd.feature_extraction.DCCRN
-  tools_for_loss.py       -> clskd.tools_for_loss.si_snr
+  tools_for_loss.py       -> clskd.tools_for_loss (si_snr, sdr, si_sdr, melFilterBank,
+                             get_array_mel_loss)
+  DCCRN.loss              -> clskd.model.DCCRN.loss; a training module around it:
+                             clskd.supervised.SupervisedTraining
   distill.py              -> clskd.distill.KnowledgeDistillation (training_step)
   distill_SPKD.py         -> clskd.distill.SPKDDistillation
   distill_SPKD.py / distill_MSE.py / distill_STFT.py with the asteroid DCCRNet_mini student
@@ -29,6 +32,9 @@ def __getattr__(name):
     if name == "OutputDistillation":
         from .distill_mini import OutputDistillation
         return OutputDistillation
+    if name == "SupervisedTraining":
+        from .supervised import SupervisedTraining
+        return SupervisedTraining
     if name == "DCCRNet_mini":
         from .asteroid import DCCRNet_mini
         return DCCRNet_mini

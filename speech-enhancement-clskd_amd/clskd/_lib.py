@@ -237,6 +237,14 @@ SIGNATURES = {
                                  _p, _p, _p, _i32, _i32, _p]),
     "clskd_mse_loss_grad_workspace": (_i64, [_i64]),
     "clskd_mse_loss_grad": (_i32, [_p, _p, _i64, _f32, _p, _p, _p, _i32, _p]),
+    # supervised losses (csrc/sup_loss.hip)
+    "clskd_wave_loss_workspace": (_i64, [_i32, _i32]),
+    "clskd_wave_loss": (_i32, [_p, _i64, _p, _i64, _i32, _i32, C.POINTER(C.c_float), _f32, _p, _p,
+                               _p, _p]),
+    "clskd_wave_loss_grad": (_i32, [_p, _i64, _p, _i64, _i32, _i32, _p, _p, _i64, _i32, _p]),
+    "clskd_mel_loss_workspace": (_i64, [_i32, _i32]),
+    "clskd_mel_loss": (_i32, [_p, _i32, _p, _i32, _i32, _i32, _p, _p, _f32, _i32, _p, _p]),
+    "clskd_mel_loss_bwd": (_i32, [_p, _i32, _p, _i32, _i32, _i32, _p, _f32, _p, _i32, _i32, _p]),
     "clskd_lstm_bwd": (_i32, [_p, _i64, _i64, _i64, _p, _i64, _i64, _i64, _p, _i32, _i32, _i32,
                               _i32, _p, _i32, _p, _i64, _i64, _i64, _p]),
     "clskd_spkd_grad_ranges": (_i32, [C.POINTER(C.c_void_p), C.POINTER(C.c_int32),

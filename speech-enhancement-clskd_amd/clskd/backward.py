@@ -326,6 +326,9 @@ def dccrn_backward(m, tape, enc, dec, dec_in, lstm_io, g, pg, acc_params=False, 
     tape: the forward tape; enc/dec/dec_in/lstm_io: the forward's activations.
     g: upstream gradient buffers (fp32): g['wav'] [B][L] or None; g['enc'][i] like enc[i];
        g['dec'][k] (k < 5) like dec[k]; g['dec_in'] like dec_in.  Consumed (accumulated into).
+       g['est_spec'] (optional): gradient w.r.t. the masked spectrum tape['est'][..., :514]
+       ([B][T][ld >= 514], re at f, im at 257 + f — a loss on DCCRN.forward's real / imag); added
+       to the iSTFT's spectrum gradient before the mask backward.
     pg: dict parameter -> fp32 gradient tensor (contiguous, same shape) receiving the gradients.
     join(): called before the first accumulation into g['enc'] / g['dec'] / g['dec_in'] (after
     the waveform tail and the last decoder layer's weight gradient), so a caller can produce
@@ -341,7 +344,12 @@ def dccrn_backward(m, tape, enc, dec, dec_in, lstm_io, g, pg, acc_params=False, 
 
     # ---------------- ConviSTFT + clamp + mask 'E' (DCCRN.py:207-237)
     dmask = None
-    if g.get("wav") is not None:
+    gest = g.get("est_spec")
+    if gest is not None and g.get("wav") is None:  # a spectrum-only loss
+        assert gest.shape[:2] == (B, T) and gest.shape[-1] >= 514 and gest.is_contiguous()
+        dmask = _empty(dec[-1].shape, dev)
+        ops.mask_e_bwd(tape["spec"], dec[-1], T, gest, dmask)
+    elif g.get("wav") is not None:
         frames, window, out_len = tape["frames"], tape["window"], tape["out_len"]
         dframes = _empty((B, T, 400), dev)
         ops.ola_bwd(frames, window, g["wav"], 100, out_len, 300, True, dframes)
@@ -354,6 +362,13 @@ def dccrn_backward(m, tape, enc, dec, dec_in, lstm_io, g, pg, acc_params=False, 
                                 wgrad=getattr(ops._SPLIT, "wgrad", False)):
             ops.conv([Seg(dframes, 0, SegGeom(400, T * 400, 0, 400, 1, T))], [(0, 0)], B, 1, T, 516,
                      wt, None, dest, OutMap(T * 516, 0, 516), mfma_only=True)
+        if gest is not None:
+            if gest.shape != dest.shape or not gest.is_contiguous():  # another row pitch: repitch
+                pad = _zeros(dest.shape, dev)
+                pad[..., :514] = gest[..., :514]
+                gest = pad
+            ops.check(ops.lib().clskd_axpy_f32(ops.ptr(gest), ops.ptr(dest), dest.numel(), 1.0, 1,
+                                               ops._stream()), "est_spec add")
         dmask = _empty(dec[-1].shape, dev)
         ops.mask_e_bwd(tape["spec"], dec[-1], T, dest, dmask)
 

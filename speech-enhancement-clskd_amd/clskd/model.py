@@ -368,11 +368,23 @@ class DCCRN(nn.Module):
                 {"params": biases, "weight_decay": 0.0}]
 
     def loss(self, inputs, labels, real_spec=None, img_spec=None, loss_mode="SI-SNR"):
-        """DCCRN.py:259-411 — the SI-SNR / MSE modes (the others need asteroid PMSQE / mel)."""
-        from .tools_for_loss import si_snr
+        """DCCRN.py:259-411: 'MSE', 'SDR', 'SI-SNR', 'SI-SDR', 'MSE+SI-SNR', 'SI-SNR+SI-SDR' and
+        the mel modes 'MSE+LMS', 'SDR+LMS', 'SI-SNR+LMS' (real_spec / img_spec: the real / imag
+        that forward returns) by the kernels of csrc/sup_loss.hip; the PMSQE modes need asteroid's
+        tables and raise NotImplementedError.  Returns a 0-d device tensor."""
+        from .tools_for_loss import si_snr, spectrum_pair
         if loss_mode == "SI-SNR":
             return -si_snr(inputs, labels)
-        raise NotImplementedError(f"loss_mode {loss_mode!r} is not on the CLSKD hot path")
+        from .supervised import LOSS_MODES, check_mode, menu_loss
+        check_mode(loss_mode)
+        clean = est = None
+        if LOSS_MODES[loss_mode][1] != 0.0:
+            if real_spec is None or img_spec is None:
+                raise ValueError(f"loss_mode {loss_mode!r} needs real_spec and img_spec")
+            labels2 = labels.reshape(-1, labels.shape[-1]).float().contiguous()
+            clean = self.spectrum(labels2)
+            est = spectrum_pair(real_spec, img_spec)
+        return menu_loss(loss_mode, inputs, labels, clean, est)[0]
 
     # ---------------------------------------------------------------- packed weights
     @staticmethod

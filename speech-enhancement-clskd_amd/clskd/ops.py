@@ -1552,6 +1552,138 @@ def mse_loss_grad(a, b, loss_out, da=None, scale=1.0, accumulate=False):
     return loss_out
 
 
+# ------------------------------------------------------------------------------------------
+# supervised losses (csrc/sup_loss.hip): DCCRN.loss's waveform terms and the mel distance
+# ------------------------------------------------------------------------------------------
+WAVE_TERMS = ("MSE", "SDR", "SI-SNR", "SI-SDR", "SI-SDR-swapped")
+
+
+def _rows(t):
+    """[B, L] fp32 view with unit inner stride (copied only when it has none)."""
+    t = t.reshape(-1, t.shape[-1])
+    if t.dtype != torch.float32:
+        t = t.float()
+    if t.stride(-1) != 1 or (t.shape[0] > 1 and t.stride(0) < t.shape[1]):
+        t = t.contiguous()
+    return t
+
+
+def wave_loss(s, y, weights, upstream=1.0, want_coef=True):
+    """The five waveform terms of DCCRN.loss from one pass over the estimate s and labels y
+    ([B, L] fp32, any row stride): returns (out6, coef) with out6[0] = sum_k weights[k] * l_k,
+    out6[1:] = (mse, -sdr(y, s), -si_snr(s, y), -si_sdr(y, s), -si_sdr(s, y)) and coef [B, 2] =
+    upstream * (p_b, p_b + q_b), d out6[0] / d s_b = p_b s_b + q_b y_b (None unless want_coef)."""
+    s, y = _rows(s), _rows(y)
+    assert s.shape == y.shape and len(weights) == 5
+    B, L = s.shape
+    Lb = lib()
+    dev = s.device
+    work = torch.empty(int(Lb.clskd_wave_loss_workspace(B, L)), dtype=torch.float64, device=dev)
+    out = torch.empty(6, dtype=torch.float32, device=dev)
+    coef = torch.empty(B, 2, dtype=torch.float32, device=dev) if want_coef else None
+    w5 = (C.c_float * 5)(*[float(w) for w in weights])
+    check(Lb.clskd_wave_loss(ptr(s), s.stride(0), ptr(y), y.stride(0), B, L, w5, upstream,
+                             ptr(work), ptr(out), ptr(coef), _stream()), "wave_loss")
+    return out, coef
+
+
+def wave_loss_grad(s, y, coef, d_wav, accumulate=False):
+    """d_wav[b] (+)= coef[b, 0] * (s[b] - y[b]) + coef[b, 1] * y[b] (d_wav [B, L] fp32, unit inner
+    stride): the gradient of wave_loss's out6[0], coef being its table."""
+    s, y = _rows(s), _rows(y)
+    B, L = s.shape
+    assert d_wav.shape == s.shape and d_wav.stride(-1) == 1 and d_wav.dtype == torch.float32
+    assert coef.shape == (B, 2) and coef.is_contiguous()
+    check(lib().clskd_wave_loss_grad(ptr(s), s.stride(0), ptr(y), y.stride(0), B, L, ptr(coef),
+                                     ptr(d_wav), d_wav.stride(0), int(accumulate), _stream()),
+          "wave_loss_grad")
+    return d_wav
+
+
+MEL_SCALES = (16, 32, 64)
+MEL_FILTERS = 112
+MEL_TABLE_WORDS = 112 * 257 + 112 * 2 + 257 * 6 + 257 * 6  # include/clskd.h CLSKD_MEL_TABLE_WORDS
+_MEL_TABLES = {}
+
+
+def mel_table_host(banks):
+    """The kernels' filter table (include/clskd.h) as an int32 numpy array, from the three
+    [S][257] filterbank matrices (melFilterBank(16 | 32 | 64, 512))."""
+    import numpy as np
+    W = np.concatenate([np.asarray(b, dtype=np.float64) for b in banks], 0).astype(np.float32)
+    assert W.shape == (MEL_FILTERS, 257), W.shape
+    supp = np.zeros((MEL_FILTERS, 2), np.int32)
+    for k in range(MEL_FILTERS):
+        nz = np.nonzero(W[k])[0]
+        if nz.size == 0:
+            raise ValueError(f"mel filter {k} is empty")
+        supp[k] = (nz[0], nz[-1] + 1)
+    pk = np.zeros((257, 6), np.int32)
+    pw = np.zeros((257, 6), np.float32)
+    k0 = 0
+    for si, S in enumerate(MEL_SCALES):
+        for j in range(257):
+            nz = np.nonzero(W[k0:k0 + S, j])[0]
+            if nz.size > 2:
+                raise ValueError(f"mel scale {S}: position {j} lies under {nz.size} filters")
+            for i, k in enumerate(nz):
+                pk[j, 2 * si + i] = k0 + k
+                pw[j, 2 * si + i] = W[k0 + k, j]
+        k0 += S
+    tab = np.concatenate([W.view(np.int32).reshape(-1), supp.reshape(-1), pk.reshape(-1),
+                          pw.view(np.int32).reshape(-1)])
+    assert tab.size == MEL_TABLE_WORDS
+    return tab
+
+
+def mel_table(device):
+    """Device copy of the filter table, built once per device."""
+    key = torch.device(device)
+    t = _MEL_TABLES.get(key)
+    if t is None:
+        from .tools_for_loss import melFilterBank
+        tab = mel_table_host([melFilterBank(S, 512) for S in MEL_SCALES])
+        t = _MEL_TABLES[key] = torch.from_numpy(tab).to(key)
+    return t
+
+
+def _spec3(t):
+    assert t.dim() == 3 and t.dtype == torch.float32 and t.shape[-1] >= 514 and t.is_contiguous(), \
+        "spectrum: contiguous fp32 [B][T][ld >= 514]"
+    return t
+
+
+def mel_loss(clean, est, out2=None, scale=1.0, accumulate=False, table=None):
+    """get_array_mel_loss of two frame-major spectra [B][T][ld >= 514] (clean: DCCRN.spectrum,
+    est: the masked spectrum tape['est']): out2[0] (+)= scale * loss, out2[1] = loss."""
+    clean, est = _spec3(clean), _spec3(est)
+    B, T = est.shape[:2]
+    assert clean.shape[:2] == (B, T)
+    Lb = lib()
+    dev = est.device
+    table = mel_table(dev) if table is None else table
+    assert table.numel() == MEL_TABLE_WORDS and table.dtype == torch.int32
+    if out2 is None:
+        out2 = torch.empty(2, dtype=torch.float32, device=dev)
+    work = torch.empty(int(Lb.clskd_mel_loss_workspace(B, T)), dtype=torch.float64, device=dev)
+    check(Lb.clskd_mel_loss(ptr(clean), clean.shape[-1], ptr(est), est.shape[-1], B, T, ptr(table),
+                            ptr(work), scale, int(accumulate), ptr(out2), _stream()), "mel_loss")
+    return out2
+
+
+def mel_loss_bwd(clean, est, d_est, upstream=1.0, accumulate=False, table=None):
+    """d_est [B][T][ld >= 514] (+)= upstream * d mel_loss / d est (columns >= 514 untouched)."""
+    clean, est, d_est = _spec3(clean), _spec3(est), _spec3(d_est)
+    B, T = est.shape[:2]
+    assert clean.shape[:2] == (B, T) and d_est.shape[:2] == (B, T)
+    table = mel_table(est.device) if table is None else table
+    assert table.numel() == MEL_TABLE_WORDS and table.dtype == torch.int32
+    check(lib().clskd_mel_loss_bwd(ptr(clean), clean.shape[-1], ptr(est), est.shape[-1], B, T,
+                                   ptr(table), upstream, ptr(d_est), d_est.shape[-1],
+                                   int(accumulate), _stream()), "mel_loss_bwd")
+    return d_est
+
+
 def lstm_bwd(pre, p_strides, dh, d_strides, whh, nws, nseq, T, H, dgates, g_strides, cells=None):
     """cells: the forward's cell states (lstm_recurrent_pre's cbuf), else recomputed here."""
     c_ready = cells is not None
