@@ -154,9 +154,9 @@ typedef struct {
  * invstd, shift = beta - mean * scale; batch mean / var (biased) optionally; running statistics
  * updated n_updates times with the unbiased variance (as clskd_bn_finalize).
  * clskd_bn_fold_state_size(C): int64 elements of acc for C channels (CLSKD_BN_FOLD_REPL replicas).
- * clskd_conv_fold_capable(d): 1 if the kernel d dispatches to folds the finalize (the persistent
- *                     engines: conv_gemm8, conv_halo, conv_halo_f32), else 0 (use `stats` +
- *                     clskd_bn_finalize).
+ * clskd_conv_fold_capable(d): 1 if the engine d dispatches to (clskd_conv_route) folds the
+ *                     finalize (the persistent engines: conv_gemm8, the halo and split-product
+ *                     kernels), else 0 (use `stats` + clskd_bn_finalize).
  * -------------------------------------------------------------------------------------- */
 #define CLSKD_BN_FOLD_REPL 8
 typedef struct clskd_bn_fold_s {
@@ -185,6 +185,11 @@ int clskd_abf_bn1_fold(const float* s, int32_t B, int32_t F, int32_t T, int64_t 
                        int64_t sT, int32_t cin, const float* w1, const clskd_bn_fold* fold,
                        int32_t nblk, void* stream);
 int32_t clskd_conv_fold_capable(const clskd_conv_desc* d);
+/* The engine d dispatches to under the current knobs: its name in the dispatch table ("direct",
+ * "halo", "halow" (experiments build), "gemm8", "lds_dma", "pointwise", "halo_split", "split3",
+ * "halo_f32", "igemm_f32"; a static string).  Pure host: nothing is launched and no pointer of d
+ * is dereferenced.  NULL, with clskd_last_error() set, for a descriptor clskd_conv2d_fwd refuses. */
+const char* clskd_conv_route(const clskd_conv_desc* d);
 
 #define CLSKD_WLAYOUT_NK 0
 #define CLSKD_WLAYOUT_DIRECT 1

@@ -156,6 +156,7 @@ SIGNATURES = {
     "clskd_experiments_build": (_i32, []),
     "clskd_conv2d_fwd": (_i32, [C.POINTER(ConvDesc), _p]),
     "clskd_conv_fold_capable": (_i32, [C.POINTER(ConvDesc)]),
+    "clskd_conv_route": (C.c_char_p, [C.POINTER(ConvDesc)]),
     "clskd_conv_halo_split_plan": (_i32, [C.POINTER(ConvDesc), C.POINTER(HaloSplitInfo)]),
     "clskd_bn_fold_state_size": (_i64, [_i32]),
     "clskd_abf_bn1_fold": (_i32, [_p, _i32, _i32, _i32, _i64, _i64, _i64, _i32, _p, _p, _i32, _p]),

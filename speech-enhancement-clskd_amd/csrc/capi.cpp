@@ -32,43 +32,12 @@ void note_kernel_fn(const void* fn) { g_kernel_fn = fn; }
 struct KnobDef {
   const char* name;
   int dflt;
-  // product knobs are parity-tested dispatch routes (tests/test_gpu_parity.py); every other knob
-  // is an A/B or timing experiment: a product build holds it at its default (the environment is
-  // not read for it and clskd_set_knob refuses another value)
-  bool product;
+  bool product;  // (common.h, CLSKD_KNOBS)
 };
-// order = KnobId
 static const KnobDef kKnobs[KNOB_COUNT] = {
-    {"CLSKD_G8", 1, false},          {"CLSKD_G8_GRID", 0, true},      {"CLSKD_HALO_GRID", 0, false},
-    {"CLSKD_LSTM_NKS", 4, false},    {"CLSKD_LSTM_NKS32", 1, true},   {"CLSKD_WGRAD_WG", 4096, false},
-    {"CLSKD_NO_HALO", 0, false},     {"CLSKD_BF16_WAVES", 8, false},  {"CLSKD_BF16_STAGES", 3, false},
-    {"CLSKD_BF16_TILE", 0, false},   {"CLSKD_NO_POINTWISE", 0, false},
-    {"CLSKD_ABF_MOMENT_DIV", 1, false}, {"CLSKD_F32_WAVES", 4, false}, {"CLSKD_EXEC_GATE", 0, false},
-    {"CLSKD_NO_HALO32", 0, true},
-    {"CLSKD_HALO32_SPLIT", 0, true}, {"CLSKD_HALO32_MIN_N", 32, true}, {"CLSKD_G8_KORDER", 1, false},
-    {"CLSKD_G8_PP", 0, false},
-    {"CLSKD_F32_SPLIT", 0, true},
-    {"CLSKD_LSTM_PRIO", 0, true},
-    {"CLSKD_SPLIT_BK", 0, true},
-    {"CLSKD_HALOW", 0, false},
-    {"CLSKD_SPLIT_GRID", 0, true},
-    {"CLSKD_G8_TA", 1, true},
-    {"CLSKD_G8_SK", 1, true},
-    {"CLSKD_SPLIT_PD", 1, true},
-    {"CLSKD_SPLIT_OCC", 1, true},
-    {"CLSKD_WGRAD_DEPTH", 0, true},
-    {"CLSKD_LSTM_BWD_WAVE", 1, true},
-    {"CLSKD_SPLIT_NS2", 1, true},
-    {"CLSKD_BN_PFOLD", 1, true},
-    {"CLSKD_LSTM_PRE", 1, true},
-    {"CLSKD_ABF_BWD_BLOCKS", 2048, false},
-    {"CLSKD_WGRAD_XCD", 1, true},
-    {"CLSKD_LSTM_BWD_PIN", 1, true},
-    {"CLSKD_HALO_SPLIT", 1, true},
-    {"CLSKD_HALO_SPLIT_GRID", 0, true},
-    {"CLSKD_LSTM128_TDIV", 0, false},
-    {"CLSKD_LSTM32_TDIV", 0, false}, {"CLSKD_BF16_DEBUG_MODE", 0, false}, {"CLSKD_SKIP", 0, false},
-    {"CLSKD_H32_DEBUG_MODE", 0, false},
+#define X(name, dflt, product) {"CLSKD_" #name, dflt, product},
+    CLSKD_KNOBS(X)
+#undef X
 };
 #ifdef CLSKD_EXPERIMENTS
 static constexpr bool kAllKnobs = true;

@@ -17,14 +17,30 @@ void note_kernel(const char* fmt, ...);
 // Host function of that kernel (clskd_conv_last_kernel_fn: the executor's per-kernel timing key).
 void note_kernel_fn(const void* fn);
 // Dispatch knobs (capi.cpp): env read once at first use, changed only by clskd_set_knob.
+// The one list of knobs, X(name, default, product): KNOB_<name> here and the registry entry
+// "CLSKD_<name>" in capi.cpp both come from it.  Product knobs are parity-tested dispatch routes
+// (tests/test_gpu_parity.py); every other knob is an A/B or timing experiment: a product build
+// holds it at its default (the environment is not read for it and clskd_set_knob refuses another
+// value).
+#define CLSKD_KNOBS(X) \
+  X(G8, 1, false) X(G8_GRID, 0, true) X(HALO_GRID, 0, false) X(LSTM_NKS, 4, false)             \
+  X(LSTM_NKS32, 1, true) X(WGRAD_WG, 4096, false) X(NO_HALO, 0, false) X(BF16_WAVES, 8, false) \
+  X(BF16_STAGES, 3, false) X(BF16_TILE, 0, false) X(NO_POINTWISE, 0, false)                    \
+  X(ABF_MOMENT_DIV, 1, false) X(F32_WAVES, 4, false) X(EXEC_GATE, 0, false)                    \
+  X(NO_HALO32, 0, true) X(HALO32_SPLIT, 0, true) X(HALO32_MIN_N, 32, true)                     \
+  X(G8_KORDER, 1, false) X(G8_PP, 0, false) X(F32_SPLIT, 0, true) X(LSTM_PRIO, 0, true)        \
+  X(SPLIT_BK, 0, true) X(HALOW, 0, false) X(SPLIT_GRID, 0, true) X(G8_TA, 1, true)             \
+  X(G8_SK, 1, true) X(SPLIT_PD, 1, true) X(SPLIT_OCC, 1, true) X(WGRAD_DEPTH, 0, true)         \
+  X(LSTM_BWD_WAVE, 1, true) X(SPLIT_NS2, 1, true) X(BN_PFOLD, 1, true) X(LSTM_PRE, 1, true)    \
+  X(ABF_BWD_BLOCKS, 2048, false) X(WGRAD_XCD, 1, true) X(LSTM_BWD_PIN, 1, true)                \
+  X(HALO_SPLIT, 1, true) X(HALO_SPLIT_GRID, 0, true)                                           \
+  /* timing-only experiment modes (wrong results): -DCLSKD_EXPERIMENTS builds only */          \
+  X(LSTM128_TDIV, 0, false) X(LSTM32_TDIV, 0, false) X(BF16_DEBUG_MODE, 0, false)              \
+  X(SKIP, 0, false) X(H32_DEBUG_MODE, 0, false)
 enum KnobId {
-  KNOB_G8, KNOB_G8_GRID, KNOB_HALO_GRID, KNOB_LSTM_NKS, KNOB_LSTM_NKS32,
-  KNOB_WGRAD_WG, KNOB_NO_HALO, KNOB_BF16_WAVES, KNOB_BF16_STAGES, KNOB_BF16_TILE,
-  KNOB_NO_POINTWISE, KNOB_ABF_MOMENT_DIV, KNOB_F32_WAVES, KNOB_EXEC_GATE,
-  KNOB_NO_HALO32, KNOB_HALO32_SPLIT, KNOB_HALO32_MIN_N, KNOB_G8_KORDER, KNOB_G8_PP, KNOB_F32_SPLIT, KNOB_LSTM_PRIO, KNOB_SPLIT_BK, KNOB_HALOW, KNOB_SPLIT_GRID, KNOB_G8_TA, KNOB_G8_SK, KNOB_SPLIT_PD, KNOB_SPLIT_OCC, KNOB_WGRAD_DEPTH, KNOB_LSTM_BWD_WAVE, KNOB_SPLIT_NS2, KNOB_BN_PFOLD, KNOB_LSTM_PRE, KNOB_ABF_BWD_BLOCKS, KNOB_WGRAD_XCD, KNOB_LSTM_BWD_PIN,
-  KNOB_HALO_SPLIT, KNOB_HALO_SPLIT_GRID,
-  // timing-only experiment modes (wrong results): -DCLSKD_EXPERIMENTS builds only
-  KNOB_LSTM128_TDIV, KNOB_LSTM32_TDIV, KNOB_BF16_DEBUG_MODE, KNOB_SKIP, KNOB_H32_DEBUG_MODE,
+#define X(name, dflt, product) KNOB_##name,
+  CLSKD_KNOBS(X)
+#undef X
   KNOB_COUNT
 };
 int knob(KnobId k);

@@ -15,7 +15,7 @@
 // every read lane group of 16 rows hits 16 distinct bank slots.  All LDS is one dynamic array.
 #include <stdlib.h>
 
-#include "common.h"
+#include "conv_dispatch.h"
 
 namespace clskd {
 
@@ -412,10 +412,7 @@ static int launch_v2(const clskd_conv_desc& d, hipStream_t st) {
   }
   const int64_t M = (int64_t)d.B * d.Fo * d.To;
   ConvArgsV2 a{d, 1, d.K / BK};
-  if (knob(KNOB_G8_KORDER) != 0 && d.ntaps > 1 && d.ctot % BK == 0 && (int64_t)d.ntaps * d.ctot == d.K) {
-    a.kt_taps = d.ntaps;
-    a.kt_cpt = d.ctot / BK;
-  }
+  conv_k_order(d, BK, true, a.kt_taps, a.kt_cpt);
   hipLaunchKernelGGL(kern, dim3((unsigned)cdiv(M, BM), (unsigned)cdiv(d.N, BN)), dim3(NW * 64), lds, st, a);
   note_kernel_fn((const void*)kern);
   note_kernel("conv_igemm_bf16_dma<%d,%d,%d,%d,%d,%s,%d>", BM, BK, BN, NW, S, type_name<OutT>(), DBG);
@@ -445,54 +442,32 @@ static int launch_big_s(const clskd_conv_desc& d, hipStream_t st) {
 // encoder/ABF layers; five or six measured no better (tools/conv_micro.py, CLSKD sweep).
 static int launch_big(const clskd_conv_desc& d, hipStream_t st) { return launch_big_s<4, 4>(d, st); }
 
+// The generic 16-bit engine: accumulating launches (fp32 out += conv: the split-product data
+// gradients over bf16 hi / lo planes; the one engine with the read-add-write epilogue) and every
+// layer neither the halo kernels nor conv_gemm8 take (short or ragged clips, halo tiles that do
+// not fit LDS; no launch in the C2-C5 censuses).  bf16 only: an f16 layer that reaches it is an
+// error, never a silent bf16 computation.
+//
 // 8 waves (512 threads) per workgroup: twice the LDS-DMA issuers of a 4-wave tile — the
 // engine is bound by DMA issue/latency, not MFMA (tools/conv_micro.py: 13-25 % faster for
 // BN >= 64).  BN = 32 keeps 4 waves (four 32x32 MFMA tiles).  CLSKD_BF16_WAVES=4 selects the
 // 4-wave tiles everywhere (A/B measurements).
-int launch_conv_halo(const clskd_conv_desc& d, hipStream_t st, bool* launched);
-int launch_conv_gemm8(const clskd_conv_desc& d, hipStream_t st, bool* launched);
-#ifdef CLSKD_EXPERIMENTS
-int launch_conv_halow(const clskd_conv_desc& d, hipStream_t st, bool* launched);
-#endif
-
-int launch_conv_bf16(const clskd_conv_desc& d, hipStream_t st) {
-  const bool no_halo = knob(KNOB_NO_HALO) == 1;  // A/B switch: 1 keeps narrow layers on the engine
-  // accumulating launches (fp32 out += conv: the split-product data gradients over bf16 hi / lo
-  // planes) run the LDS-DMA engine, the one with the read-add-write epilogue
-  if (d.accumulate) {
+int conv_lds_dma(const clskd_conv_desc& d, const hipStream_t* stp, bool* took) {
+  *took = true;
+  if (d.accumulate)
     CLSKD_CHECK_ARG(d.out_dtype == CLSKD_F32 && !d.stats && !d.bn_fold && d.in_dtype == CLSKD_BF16,
                     "conv2d(bf16): accumulate needs an fp32 output, bf16 operands, no statistics");
-    return launch_nw<8, 3>(d, st);
-  }
-  if (!no_halo) {
-    bool launched = false;
-    const int rc = launch_conv_halo(d, st, &launched);
-    if (rc != CLSKD_OK || launched) return rc;
-  }
   const int dbg = knob(KNOB_BF16_DEBUG_MODE);
   {
     const int rc = experiment_guard("CLSKD_BF16_DEBUG_MODE", dbg);
     if (rc != CLSKD_OK) return rc;
   }
-#ifdef CLSKD_EXPERIMENTS
-  if (dbg == 0 && knob(KNOB_G8) < 10) {  // the wide layers: halo tiles with streamed weights
-    bool launched = false;
-    const int rc = launch_conv_halow(d, st, &launched);
-    if (rc != CLSKD_OK || launched) return rc;
-  }
-#endif
-  if (dbg == 0) {
-    bool launched = false;
-    const int rc = launch_conv_gemm8(d, st, &launched);
-    if (rc != CLSKD_OK || launched) return rc;
-  }
-  // the generic fallback: every bf16 layer neither the halo kernel nor the persistent engine
-  // takes (short or ragged clips, halo tiles that do not fit LDS; no launch in the C2-C5
-  // censuses).  bf16 only: an f16 layer that reaches it is an error, never a silent bf16
-  // computation
   CLSKD_CHECK_ARG(d.in_dtype == CLSKD_BF16,
                   "conv2d(f16): N=%d K=%d nseg=%d fits neither the halo kernel nor conv_gemm8", d.N,
                   d.K, d.nseg);
+  if (!stp) return CLSKD_OK;
+  const hipStream_t st = *stp;
+  if (d.accumulate) return launch_nw<8, 3>(d, st);
   const int nw = knob(KNOB_BF16_WAVES) == 4 ? 4 : 8;
   const int stages = knob(KNOB_BF16_STAGES) == 4 ? 4 : 3;  // experiment knob: 3 | 4
   const int tilecfg = knob(KNOB_BF16_TILE);  // A/B knob: 128 | 256 forces one row-tile height

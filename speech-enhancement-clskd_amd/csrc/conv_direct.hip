@@ -12,7 +12,7 @@
 // SGPR operands — v_fma_f32 for fp32 runs, v_dot2c_f32_bf16 (bf16 pairs, fp32 accumulate) for
 // bf16 runs.  Each row's A run is read straight from global memory (an L1/L2-resident
 // neighbourhood) with a kvec-wide load, prefetched one run ahead.
-#include "common.h"
+#include "conv_dispatch.h"
 
 namespace clskd {
 
@@ -325,7 +325,9 @@ static void launch_g(const clskd_conv_desc& d, hipStream_t st) {
   else launch_np<64, G, InT>(d, st);
 }
 
-int launch_conv_direct(const clskd_conv_desc& d, hipStream_t st) {
+// Every DIRECT-layout descriptor is this kernel's; one it cannot run is refused, launch or not.
+int conv_direct(const clskd_conv_desc& d, const hipStream_t* stp, bool* took) {
+  *took = true;
   CLSKD_CHECK_SHAPE(conv_direct_ok(d.N, d.K), "conv2d(direct): N=%d K=%d outside the direct path",
                     d.N, d.K);
   CLSKD_CHECK_ARG(((uintptr_t)d.weight & 15) == 0, "conv2d(direct): weight must be 16-byte aligned");
@@ -334,12 +336,9 @@ int launch_conv_direct(const clskd_conv_desc& d, hipStream_t st) {
   int g = d.kvec;
   if (g == 0) g = is_lowp(d.in_dtype) ? 8 : (d.vec4 ? 4 : 1);
   CLSKD_CHECK_SHAPE(d.K % g == 0, "conv2d(direct): K=%d not a multiple of kvec %d", d.K, g);
-  if (d.in_dtype == CLSKD_BF16) {
-    CLSKD_CHECK_SHAPE(g == 8, "conv2d(direct): bf16 segments need kvec 8");
-    launch_g<8, __bf16>(d, st);
-  } else if (d.in_dtype == CLSKD_F16) {
-    CLSKD_CHECK_SHAPE(g == 8, "conv2d(direct): f16 segments need kvec 8");
-    launch_g<8, _Float16>(d, st);
+  if (is_lowp(d.in_dtype)) {
+    CLSKD_CHECK_SHAPE(g == 8, "conv2d(direct): %s segments need kvec 8",
+                      d.in_dtype == CLSKD_BF16 ? "bf16" : "f16");
   } else {
     for (int s = 0; s < d.nseg; ++s) {
       const clskd_seg& sg = d.seg[s];
@@ -347,11 +346,15 @@ int launch_conv_direct(const clskd_conv_desc& d, hipStream_t st) {
                           sg.sT % g == 0,
                       "conv2d(direct): segment %d not aligned for kvec %d", s, g);
     }
-    if (g == 4) launch_g<4, float>(d, st);
-    else if (g == 2) launch_g<2, float>(d, st);
-    else if (g == 1) launch_g<1, float>(d, st);
-    else CLSKD_CHECK_SHAPE(false, "conv2d(direct): fp32 kvec %d unsupported", g);
+    CLSKD_CHECK_SHAPE(g == 4 || g == 2 || g == 1, "conv2d(direct): fp32 kvec %d unsupported", g);
   }
+  if (!stp) return CLSKD_OK;
+  const hipStream_t st = *stp;
+  if (d.in_dtype == CLSKD_BF16) launch_g<8, __bf16>(d, st);
+  else if (d.in_dtype == CLSKD_F16) launch_g<8, _Float16>(d, st);
+  else if (g == 4) launch_g<4, float>(d, st);
+  else if (g == 2) launch_g<2, float>(d, st);
+  else launch_g<1, float>(d, st);
   return CLSKD_OK;
 }
 

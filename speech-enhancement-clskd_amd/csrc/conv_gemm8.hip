@@ -33,7 +33,7 @@
 #include <unordered_map>
 
 #include "bnfold.h"
-#include "common.h"
+#include "conv_dispatch.h"
 
 namespace clskd {
 
@@ -1017,10 +1017,7 @@ static int launch_g8(const clskd_conv_desc& d, hipStream_t st) {
     }
   }
   // channel-block-major K order when every K-tile lies inside one tap (CLSKD_G8_KORDER=0: packed)
-  if (knob(KNOB_G8_KORDER) != 0 && d.ntaps > 1 && d.ctot % BK == 0 && (int64_t)d.ntaps * d.ctot == d.K) {
-    a.kt_taps = d.ntaps;
-    a.kt_cpt = d.ctot / BK;
-  }
+  conv_k_order(d, BK, true, a.kt_taps, a.kt_cpt);
   const void* kfn = (const void*)kern;
   if constexpr (TA == 1) {
     if (a.sk_cnt) {  // the stream-K instantiation
@@ -1066,28 +1063,22 @@ static bool g8_ta_ok(const clskd_conv_desc& d) {
   return (int64_t)d.N * d.K * 2 < ((int64_t)1 << 31) - 64;
 }
 
-// Entry from launch_conv_bf16 for N > 64 bf16 layers.  *launched = false leaves the layer to the
-// older engine (CLSKD_G8=0 selects that everywhere; an A/B switch).  CLSKD_G8 = 10*cfg + dbg
-// selects timing-experiment variants (bf16 outputs only); read per launch (tests switch it).
-// Whether launch_conv_gemm8 would take the layer (default mode).
-bool conv_gemm8_takes(const clskd_conv_desc& d) {
-  return knob(KNOB_G8) != 0 && d.N > 64 && d.K % 64 == 0 && d.nseg <= 2 &&
-         (int64_t)d.B * d.Fo * d.To < ((int64_t)1 << 31) && (int64_t)d.Fo * d.stride_f < 32768 &&
-         (int64_t)d.To * d.stride_t < 32768;
-}
-
-int launch_conv_gemm8(const clskd_conv_desc& d, hipStream_t st, bool* launched) {
-  *launched = false;
+// The N > 64 16-bit layers.  *took = false leaves the layer to the older engine (CLSKD_G8=0
+// selects that everywhere; an A/B switch).  CLSKD_G8 = 10*cfg + dbg selects timing-experiment
+// variants (bf16 outputs only); read per launch (tests switch it).
+int conv_gemm8(const clskd_conv_desc& d, const hipStream_t* stp, bool* took) {
+  *took = false;
   const int mode = knob(KNOB_G8);
   if (mode >= 10) {
     const int rc = experiment_guard("CLSKD_G8", mode);
     if (rc != CLSKD_OK) return rc;
   }
-  if (mode == 0 || d.N <= 64 || d.K % 64 != 0 || d.nseg > 2 || (int64_t)d.B * d.Fo * d.To >= ((int64_t)1 << 31) ||
-      (int64_t)d.Fo * d.stride_f >= 32768 || (int64_t)d.To * d.stride_t >= 32768)  // 16-bit row origins
-    return CLSKD_OK;
+  *took = mode != 0 && d.N > 64 && d.K % 64 == 0 && d.nseg <= 2 &&
+          (int64_t)d.B * d.Fo * d.To < ((int64_t)1 << 31) &&
+          (int64_t)d.Fo * d.stride_f < 32768 && (int64_t)d.To * d.stride_t < 32768;  // 16-bit row origins
+  if (!*took || !stp) return CLSKD_OK;
+  const hipStream_t st = *stp;
   const bool f32 = d.out_dtype == CLSKD_F32;
-  *launched = true;
 #ifdef CLSKD_EXPERIMENTS
   if (mode >= 100 && !f32 && d.in_dtype == CLSKD_BF16 && g8_ta_ok(d)) {
     // TA ablations (round 6): CLSKD_G8 = 100 + ABL flags (see the kernel's DBG >= 16 note)

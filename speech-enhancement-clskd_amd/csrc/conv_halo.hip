@@ -22,6 +22,7 @@
 // table, the DMA slot word and the statistics reduction are conv_halo_common.h's.
 #include <stdlib.h>
 
+#include "conv_dispatch.h"
 #include "conv_halo_common.h"
 
 #ifndef HALO_TRACE
@@ -334,21 +335,13 @@ static bool halo_decide(const clskd_conv_desc& d, HaloArgs (&a)[2], size_t (&lds
 
 static void launch_halo_planned(const HaloArgs& a, size_t lds, hipStream_t st);
 
-// Whether launch_conv_halo would take the layer (the same decision, nothing launched).
-bool conv_halo_takes(const clskd_conv_desc& d) {
+int conv_halo(const clskd_conv_desc& d, const hipStream_t* st, bool* took) {
   HaloArgs a[2];
   size_t lds[2] = {0, 0};
   int n = 0;
-  return halo_decide(d, a, lds, n);
-}
-
-int launch_conv_halo(const clskd_conv_desc& d, hipStream_t st, bool* launched) {
-  HaloArgs a[2];
-  size_t lds[2] = {0, 0};
-  int n = 0;
-  *launched = halo_decide(d, a, lds, n);
-  if (*launched)
-    for (int i = 0; i < n; ++i) launch_halo_planned(a[i], lds[i], st);
+  *took = halo_decide(d, a, lds, n);
+  if (*took && st)
+    for (int i = 0; i < n; ++i) launch_halo_planned(a[i], lds[i], *st);
   return CLSKD_OK;
 }
 

@@ -25,6 +25,7 @@
 // table, the DMA slot word and the statistics reduction are conv_halo_common.h's.
 #include <stdlib.h>
 
+#include "conv_dispatch.h"
 #include "conv_halo_common.h"
 
 namespace clskd {
@@ -427,21 +428,13 @@ static void launch_halo32_planned(const Halo32Args& a, size_t lds, hipStream_t s
 #undef H32_LAUNCH
 }
 
-// Whether launch_conv_halo_f32 would take the layer (the same decision, nothing launched).
-bool conv_halo_f32_takes(const clskd_conv_desc& d) {
+int conv_halo_f32(const clskd_conv_desc& d, const hipStream_t* st, bool* took) {
   Halo32Args a[2];
   size_t lds[2] = {0, 0};
   int n = 0;
-  return halo32_decide(d, a, lds, n);
-}
-
-int launch_conv_halo_f32(const clskd_conv_desc& d, hipStream_t st, bool* launched) {
-  Halo32Args a[2];
-  size_t lds[2] = {0, 0};
-  int n = 0;
-  *launched = halo32_decide(d, a, lds, n);
-  if (*launched)
-    for (int i = 0; i < n; ++i) launch_halo32_planned(a[i], lds[i], st);
+  *took = halo32_decide(d, a, lds, n);
+  if (*took && st)
+    for (int i = 0; i < n; ++i) launch_halo32_planned(a[i], lds[i], *st);
   return CLSKD_OK;
 }
 

@@ -44,6 +44,7 @@
 // conv_halo_common.h's; clskd_conv_halo_split_plan walks the staging loads with the same helpers.
 #include <stdlib.h>
 
+#include "conv_dispatch.h"
 #include "conv_halo_common.h"
 
 namespace clskd {
@@ -478,18 +479,11 @@ static void launch_halo_split_planned(const HaloSplitArgs& a, size_t lds, hipStr
 #undef HS3_LAUNCH
 }
 
-// Whether launch_conv_halo_split would take the layer (the same decision, nothing launched).
-bool conv_halo_split_takes(const clskd_conv_desc& d) {
+int conv_halo_split(const clskd_conv_desc& d, const hipStream_t* st, bool* took) {
   HaloSplitArgs a;
   size_t lds = 0;
-  return halo_split_decide(d, a, lds);
-}
-
-int launch_conv_halo_split(const clskd_conv_desc& d, hipStream_t st, bool* launched) {
-  HaloSplitArgs a;
-  size_t lds = 0;
-  *launched = halo_split_decide(d, a, lds);
-  if (*launched) launch_halo_split_planned(a, lds, st);
+  *took = halo_split_decide(d, a, lds);
+  if (*took && st) launch_halo_split_planned(a, lds, *st);
   return CLSKD_OK;
 }
 

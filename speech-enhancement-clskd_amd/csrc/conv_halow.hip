@@ -31,6 +31,7 @@
 // 256-column instances measured 2-5 us slower (profiles/halo_common_micro.txt).
 #include <stdlib.h>
 
+#include "conv_dispatch.h"
 #include "conv_halo_common.h"
 
 namespace clskd {
@@ -455,20 +456,13 @@ static bool halow_decide(const clskd_conv_desc& d, HwArgs& a, size_t& lds, int& 
   return d.ntaps == 4 || d.ntaps == 6 || d.ntaps == 9 || d.ntaps == 10;
 }
 
-// Whether launch_conv_halow would take the layer (the same decision, nothing launched).
-bool conv_halow_takes(const clskd_conv_desc& d) {
+int conv_halow(const clskd_conv_desc& d, const hipStream_t* stp, bool* took) {
   HwArgs a;
   size_t lds = 0;
   int tt = 0, bn = 0;
-  return halow_decide(d, a, lds, tt, bn);
-}
-
-int launch_conv_halow(const clskd_conv_desc& d, hipStream_t st, bool* launched) {
-  HwArgs a;
-  size_t lds = 0;
-  int tt = 0, bn = 0;
-  *launched = halow_decide(d, a, lds, tt, bn);
-  if (!*launched) return CLSKD_OK;
+  *took = halow_decide(d, a, lds, tt, bn);
+  if (!*took || !stp) return CLSKD_OK;
+  const hipStream_t st = *stp;
   const int ncu = device_cu_count();
   // persistent grid; with partial statistics slots (one per workgroup) at most ceil(M/128)
   int grid = a.g.ntiles < ncu ? a.g.ntiles : ncu;

@@ -13,7 +13,7 @@
 // groups hit 16 distinct bank slots.
 #include <stdlib.h>
 
-#include "common.h"
+#include "conv_dispatch.h"
 
 namespace clskd {
 
@@ -330,49 +330,137 @@ __global__ __launch_bounds__(NW * 64) void conv_igemm_f32(const ConvArgs args) {
   }
 }
 
-int launch_conv_bf16(const clskd_conv_desc& d, hipStream_t st);
+// The generic fp32 engine: every fp32 layer no other engine takes.
+int conv_generic_f32(const clskd_conv_desc& d, const hipStream_t* stp, bool* took) {
+  *took = true;
+  const size_t ctab_bytes = (size_t)(d.K / 4) * 8;  // VEC4 K-chunk table (dynamic LDS)
+  CLSKD_CHECK_SHAPE(!d.vec4 || ctab_bytes <= 32 * 1024, "conv2d(f32): K=%d too long for the chunk table", d.K);
+  if (!stp) return CLSKD_OK;
+  const hipStream_t st = *stp;
+  const int64_t M = (int64_t)d.B * d.Fo * d.To;
+  ConvArgs a{d, 1, d.K / BK};
+  if (d.vec4) conv_k_order(d, BK, true, a.kt_taps, a.kt_cpt);
+  // 8-wave 256-row tiles (A/B knob CLSKD_F32_WAVES=4|8): half the B staging per FLOP and two
+  // waves per SIMD to hide the gather latency
+  const int nw = knob(KNOB_F32_WAVES) == 8 ? 8 : 4;
+#define LAUNCH(BN_, V_, O_, NW_)                                                             \
+  do {                                                                                       \
+    hipLaunchKernelGGL((conv_igemm_f32<BN_, V_, O_, NW_>),                             \
+                       dim3((unsigned)cdiv(M, 32 * NW_), (unsigned)cdiv(d.N, BN_)),           \
+                       dim3(NW_ * 64), (V_) ? ctab_bytes : 0, st, a);                        \
+    note_kernel_fn((const void*)conv_igemm_f32<BN_, V_, O_, NW_>);                    \
+    note_kernel("conv_igemm_f32<%d,%s,%s,%d>", BN_, (V_) ? "true" : "false",                  \
+                type_name<O_>(), NW_);                                                       \
+  } while (0)
+#define LAUNCH_NW(BN_, V_, O_) \
+  do { if (nw == 8) LAUNCH(BN_, V_, O_, 8); else LAUNCH(BN_, V_, O_, 4); } while (0)
+#define LAUNCH_O(BN_, V_)                                                   \
+  do {                                                                      \
+    if (d.out_dtype == CLSKD_BF16) LAUNCH_NW(BN_, V_, __bf16);              \
+    else if (d.out_dtype == CLSKD_F16) LAUNCH_NW(BN_, V_, _Float16);        \
+    else LAUNCH_NW(BN_, V_, float);                                         \
+  } while (0)
+  if (d.N <= 32) {
+    if (d.vec4) LAUNCH_O(32, true); else LAUNCH_O(32, false);
+  } else if (d.N <= 64) {
+    if (d.vec4) LAUNCH_O(64, true); else LAUNCH_O(64, false);
+  } else {
+    if (d.vec4) LAUNCH_O(128, true); else LAUNCH_O(128, false);
+  }
+#undef LAUNCH_O
+#undef LAUNCH_NW
+#undef LAUNCH
+  return CLSKD_OK;
+}
 
-int launch_conv_direct(const clskd_conv_desc& d, hipStream_t st);
+// ---- the dispatch table: the one place that says which engine a descriptor reaches -------------
+// Rows are tried in order within the descriptor's class; the first whose gate passes and whose
+// entry takes the descriptor runs it.  The gates hold the dispatch knobs that switch a whole
+// engine off (an engine's own decide holds the rest).  fold_max_n: the widest N for which the
+// engine folds the BatchNorm finalize (clskd_bn_fold) in its epilogue; 0 = it has no such epilogue.
+enum ConvClass { CONV_DIRECT, CONV_LOWP, CONV_F32 };
+constexpr int FOLD_NEVER = 0, FOLD_ANY_N = INT32_MAX;
 
-int launch_conv_pointwise(const clskd_conv_desc& d, hipStream_t st, bool* launched);
-int launch_conv_halo_f32(const clskd_conv_desc& d, hipStream_t st, bool* launched);
-int launch_conv_split3(const clskd_conv_desc& d, hipStream_t st, bool* launched, bool force);
-int launch_conv_halo_split(const clskd_conv_desc& d, hipStream_t st, bool* launched);
+struct ConvEngine {
+  const char* name;  // clskd_conv_route's answer; "conv2d_<name>" in a launch failure's message
+  ConvClass cls;
+  ConvEntry entry;
+  bool (*gate)(const clskd_conv_desc& d, bool want_split);  // nullptr: always tried
+  int fold_max_n;
+};
+
+static const ConvEngine kConvEngines[] = {
+    {"direct", CONV_DIRECT, conv_direct, nullptr, FOLD_NEVER},
+    // 16-bit.  Accumulating launches go to the LDS-DMA engine alone; CLSKD_NO_HALO=1 keeps narrow
+    // layers off the halo kernel; the timing modes of CLSKD_BF16_DEBUG_MODE are that engine's too
+    {"halo", CONV_LOWP, conv_halo,
+     [](const clskd_conv_desc& d, bool) { return !d.accumulate && knob(KNOB_NO_HALO) != 1; }, FOLD_ANY_N},
+#ifdef CLSKD_EXPERIMENTS
+    {"halow", CONV_LOWP, conv_halow,  // the wide layers: halo tiles with streamed weights
+     [](const clskd_conv_desc& d, bool) {
+       return !d.accumulate && knob(KNOB_BF16_DEBUG_MODE) == 0 && knob(KNOB_G8) < 10;
+     },
+     FOLD_ANY_N},
+#endif
+    {"gemm8", CONV_LOWP, conv_gemm8,
+     [](const clskd_conv_desc& d, bool) { return !d.accumulate && knob(KNOB_BF16_DEBUG_MODE) == 0; },
+     256},  // one N-tile (256x256 / 256x128 instances)
+    {"lds_dma", CONV_LOWP, conv_lds_dma, nullptr, FOLD_NEVER},
+    // fp32.  1x1 channel lifts with short K: the streaming pointwise kernel
+    {"pointwise", CONV_F32, conv_pointwise, nullptr, FOLD_NEVER},
+    // split products asked for per descriptor (CLSKD_F32X3: the student of precision 'mixed'):
+    // the halo-tiled kernel first (CLSKD_HALO_SPLIT=1), then conv_split3_kernel; the global A/B
+    // knob CLSKD_F32_SPLIT=1 routes plain fp32 descriptors to conv_split3_kernel alone
+    {"halo_split", CONV_F32, conv_halo_split, [](const clskd_conv_desc&, bool split) { return split; },
+     FOLD_ANY_N},
+    {"split3", CONV_F32, conv_split3,
+     [](const clskd_conv_desc&, bool split) { return split || knob(KNOB_F32_SPLIT) == 1; }, FOLD_ANY_N},
+    // narrow tap-structured layers: the halo-tiled fp32 kernel
+    {"halo_f32", CONV_F32, conv_halo_f32,
+     [](const clskd_conv_desc&, bool) { return knob(KNOB_NO_HALO32) != 1; }, FOLD_ANY_N},
+    {"igemm_f32", CONV_F32, conv_generic_f32, nullptr, FOLD_NEVER},
+};
+
+// CLSKD_F32X3 only asks for the split engines; every fp32 engine sees the descriptor as CLSKD_F32
+static void engine_view(const clskd_conv_desc& in, clskd_conv_desc& d, bool& want_split) {
+  d = in;
+  want_split = in.compute == CLSKD_F32X3;
+  if (want_split) d.compute = CLSKD_F32;
+}
+
+// Walk the table: *row = the engine that takes d (launched on *st when st is given).
+static int conv_route(const clskd_conv_desc& d, bool want_split, const hipStream_t* st,
+                      const ConvEngine** row) {
+  *row = nullptr;
+  const ConvClass cls = d.wlayout == CLSKD_WLAYOUT_DIRECT ? CONV_DIRECT
+                        : is_lowp(d.compute)              ? CONV_LOWP
+                                                          : CONV_F32;
+  for (const ConvEngine& e : kConvEngines) {
+    if (e.cls != cls || (e.gate && !e.gate(d, want_split))) continue;
+    bool took = false;
+    const int rc = e.entry(d, st, &took);
+    if (rc != CLSKD_OK) return rc;
+    if (took) {
+      *row = &e;
+      return CLSKD_OK;
+    }
+  }
+  set_error("conv2d: no engine takes the descriptor");  // (never: each class ends on a catch-all)
+  return CLSKD_E_ARG;
+}
 
 }  // namespace clskd
 
 using namespace clskd;
 
-namespace clskd {
-bool conv_halo_takes(const clskd_conv_desc& d);
-bool conv_halo_f32_takes(const clskd_conv_desc& d);
-bool conv_gemm8_takes(const clskd_conv_desc& d);
-#ifdef CLSKD_EXPERIMENTS
-bool conv_halow_takes(const clskd_conv_desc& d);
-#endif
-bool conv_pointwise_takes(const clskd_conv_desc& d);
-bool conv_split3_takes(const clskd_conv_desc& d, bool force);
-bool conv_halo_split_takes(const clskd_conv_desc& d);
-}  // namespace clskd
-
-// The kernel a descriptor dispatches to folds the BatchNorm finalize (clskd_bn_fold): the
-// persistent engines.  Mirrors the dispatch order of clskd_conv2d_fwd.
+// The engine a descriptor dispatches to folds the BatchNorm finalize (clskd_bn_fold): the same
+// walk as the dispatch, deciding only, then the row's fold column.
 static bool fold_capable(const clskd_conv_desc& dd) {
-  if (dd.wlayout == CLSKD_WLAYOUT_DIRECT || dd.accumulate) return false;
-  if (is_lowp(dd.compute)) {
-    if (conv_halo_takes(dd)) return true;
-#ifdef CLSKD_EXPERIMENTS
-    if (conv_halow_takes(dd)) return true;
-#endif
-    return conv_gemm8_takes(dd) && dd.N <= 256;  // one N-tile (256x256 / 256x128 instances)
-  }
-  const bool split = dd.compute == CLSKD_F32X3;
-  clskd_conv_desc d = dd;  // the fp32 engines see CLSKD_F32 (F32X3 only asks for the split)
-  d.compute = CLSKD_F32;
-  if (conv_pointwise_takes(d)) return false;
-  if (split && conv_halo_split_takes(d)) return true;
-  if (conv_split3_takes(d, split)) return true;
-  return knob(KNOB_NO_HALO32) != 1 && conv_halo_f32_takes(d);
+  clskd_conv_desc d;
+  bool want_split;
+  engine_view(dd, d, want_split);
+  const ConvEngine* row;
+  return !d.accumulate && conv_route(d, want_split, nullptr, &row) == CLSKD_OK && d.N <= row->fold_max_n;
 }
 
 extern "C" int32_t clskd_conv_fold_capable(const clskd_conv_desc* dp) {
@@ -384,18 +472,15 @@ extern "C" int64_t clskd_bn_fold_state_size(int32_t C) {
   return C > 0 ? (int64_t)CLSKD_BN_FOLD_REPL * C * 6 : 0;
 }
 
-extern "C" int clskd_conv2d_fwd(const clskd_conv_desc* dp, void* stream) {
+// The argument and shape checks of clskd_conv2d_fwd; d = the engines' view of *dp.
+static int conv_check(const clskd_conv_desc* dp, clskd_conv_desc& d, bool& want_split) {
   CLSKD_CHECK_ARG(dp != nullptr, "conv2d: null descriptor");
   CLSKD_CHECK_ARG(dp->compute == CLSKD_F32 || dp->compute == CLSKD_BF16 || dp->compute == CLSKD_F16 ||
                       dp->compute == CLSKD_F32X3,
                   "conv2d: unknown compute %d", dp->compute);
   CLSKD_CHECK_ARG(dp->compute != CLSKD_F32X3 || dp->in_dtype == CLSKD_F32,
                   "conv2d: split products (CLSKD_F32X3) take fp32 segments");
-  // CLSKD_F32X3 asks for the split engine; every fp32 engine sees the descriptor as CLSKD_F32
-  const bool want_split = dp->compute == CLSKD_F32X3;
-  clskd_conv_desc dcopy = *dp;
-  if (want_split) dcopy.compute = CLSKD_F32;
-  const clskd_conv_desc& d = dcopy;
+  engine_view(*dp, d, want_split);
   CLSKD_CHECK_SHAPE(d.B > 0 && d.Fo > 0 && d.To > 0 && d.N > 0 && d.K > 0, "conv2d: empty shape");
   if (const clskd_bn_fold* f = d.bn_fold) {
     CLSKD_CHECK_ARG(!d.stats, "conv2d: bn_fold and stats are exclusive");
@@ -435,7 +520,6 @@ extern "C" int clskd_conv2d_fwd(const clskd_conv_desc* dp, void* stream) {
   }
   const int64_t M = (int64_t)d.B * d.Fo * d.To;
   CLSKD_CHECK_SHAPE(M < (int64_t)INT32_MAX * 64, "conv2d: too many rows");
-  hipStream_t st = as_stream(stream);
   CLSKD_CHECK_SHAPE(d.kvec == 0 || d.kvec == 1 || d.kvec == 2 || d.kvec == 4 || d.kvec == 8,
                     "conv2d: kvec=%d", d.kvec);
   CLSKD_CHECK_ARG(d.wlayout == CLSKD_WLAYOUT_NK || d.wlayout == CLSKD_WLAYOUT_DIRECT,
@@ -444,99 +528,32 @@ extern "C" int clskd_conv2d_fwd(const clskd_conv_desc* dp, void* stream) {
                                      d.out_dtype == CLSKD_F32),
                   "conv2d: accumulate needs fp32 or bf16 compute and an fp32 output (the fp32 "
                   "engines, the direct kernel, the bf16 LDS-DMA engine)");
-  if (d.wlayout == CLSKD_WLAYOUT_DIRECT) {
-    if (skip_kernel(SKIP_CONV_DIRECT)) return CLSKD_OK;
-    const int rc = launch_conv_direct(d, st);
-    if (rc != CLSKD_OK) return rc;
-    CLSKD_LAUNCH_CHECK("conv2d_direct");
+  return CLSKD_OK;
+}
+
+extern "C" const char* clskd_conv_route(const clskd_conv_desc* dp) {
+  clskd_conv_desc d;
+  bool want_split;
+  const ConvEngine* row;
+  if (conv_check(dp, d, want_split) != CLSKD_OK || conv_route(d, want_split, nullptr, &row) != CLSKD_OK)
+    return nullptr;
+  return row->name;
+}
+
+extern "C" int clskd_conv2d_fwd(const clskd_conv_desc* dp, void* stream) {
+  clskd_conv_desc d;
+  bool want_split;
+  if (const int rc = conv_check(dp, d, want_split)) return rc;
+  if (skip_kernel(d.wlayout == CLSKD_WLAYOUT_DIRECT ? SKIP_CONV_DIRECT
+                  : is_lowp(d.compute)              ? SKIP_CONV_LOWP
+                                                    : SKIP_CONV_F32))
     return CLSKD_OK;
+  const hipStream_t st = as_stream(stream);
+  const ConvEngine* row;
+  if (const int rc = conv_route(d, want_split, &st, &row)) return rc;
+  if (const hipError_t e = hipGetLastError(); e != hipSuccess) {  // (CLSKD_LAUNCH_CHECK, named by the row)
+    set_error("conv2d_%s: launch failed: %s", row->name, hipGetErrorString(e));
+    return CLSKD_E_HIP;
   }
-  if (lowp) {
-    if (skip_kernel(SKIP_CONV_LOWP)) return CLSKD_OK;
-    const int rc = launch_conv_bf16(d, st);
-    if (rc != CLSKD_OK) return rc;
-    CLSKD_LAUNCH_CHECK("conv2d_bf16");
-    return CLSKD_OK;
-  }
-  if (skip_kernel(SKIP_CONV_F32)) return CLSKD_OK;
-  {  // 1x1 channel lifts with short K: the streaming pointwise kernel (conv_pointwise.hip)
-    bool launched = false;
-    const int rc = launch_conv_pointwise(d, st, &launched);
-    if (rc != CLSKD_OK) return rc;
-    if (launched) {
-      CLSKD_LAUNCH_CHECK("conv2d_pointwise");
-      return CLSKD_OK;
-    }
-  }
-  // split products asked for per descriptor (CLSKD_F32X3: the student of precision 'mixed'):
-  // the halo-tiled kernel first (CLSKD_HALO_SPLIT=1).  The global A/B knob CLSKD_F32_SPLIT=1 keeps
-  // routing plain fp32 descriptors to conv_split3_kernel alone.
-  if (want_split) {
-    bool launched = false;
-    const int rc = launch_conv_halo_split(d, st, &launched);
-    if (rc != CLSKD_OK) return rc;
-    if (launched) {
-      CLSKD_LAUNCH_CHECK("conv2d_halo_split");
-      return CLSKD_OK;
-    }
-  }
-  {  // fp32-accurate 3 x bf16 split products on the bf16 MFMA pipe (CLSKD_F32X3 descriptors;
-     // every fp32 descriptor with the A/B knob CLSKD_F32_SPLIT=1)
-    bool launched = false;
-    const int rc = launch_conv_split3(d, st, &launched, want_split);
-    if (rc != CLSKD_OK) return rc;
-    if (launched) {
-      CLSKD_LAUNCH_CHECK("conv2d_split3");
-      return CLSKD_OK;
-    }
-  }
-  if (knob(KNOB_NO_HALO32) != 1) {  // narrow tap-structured layers: halo-tiled fp32 kernel
-    bool launched = false;
-    const int rc = launch_conv_halo_f32(d, st, &launched);
-    if (rc != CLSKD_OK) return rc;
-    if (launched) {
-      CLSKD_LAUNCH_CHECK("conv2d_halo_f32");
-      return CLSKD_OK;
-    }
-  }
-  ConvArgs a{d, 1, d.K / BK};
-  if (knob(KNOB_G8_KORDER) != 0 && d.vec4 && d.ntaps > 1 && d.ctot % BK == 0 &&
-      (int64_t)d.ntaps * d.ctot == d.K) {  // channel-block-major K order (CLSKD_G8_KORDER=0: packed)
-    a.kt_taps = d.ntaps;
-    a.kt_cpt = d.ctot / BK;
-  }
-  const size_t ctab_bytes = (size_t)(d.K / 4) * 8;  // VEC4 K-chunk table (dynamic LDS)
-  CLSKD_CHECK_SHAPE(!d.vec4 || ctab_bytes <= 32 * 1024, "conv2d(f32): K=%d too long for the chunk table", d.K);
-  // 8-wave 256-row tiles (A/B knob CLSKD_F32_WAVES=4|8): half the B staging per FLOP and two
-  // waves per SIMD to hide the gather latency
-  const int nw = knob(KNOB_F32_WAVES) == 8 ? 8 : 4;
-#define LAUNCH(BN_, V_, O_, NW_)                                                             \
-  do {                                                                                       \
-    hipLaunchKernelGGL((conv_igemm_f32<BN_, V_, O_, NW_>),                                    \
-                       dim3((unsigned)cdiv(M, 32 * NW_), (unsigned)cdiv(d.N, BN_)),           \
-                       dim3(NW_ * 64), (V_) ? ctab_bytes : 0, st, a);                        \
-    note_kernel_fn((const void*)conv_igemm_f32<BN_, V_, O_, NW_>);                           \
-    note_kernel("conv_igemm_f32<%d,%s,%s,%d>", BN_, (V_) ? "true" : "false",                  \
-                type_name<O_>(), NW_);                                                       \
-  } while (0)
-#define LAUNCH_NW(BN_, V_, O_) \
-  do { if (nw == 8) LAUNCH(BN_, V_, O_, 8); else LAUNCH(BN_, V_, O_, 4); } while (0)
-#define LAUNCH_O(BN_, V_)                                                   \
-  do {                                                                      \
-    if (d.out_dtype == CLSKD_BF16) LAUNCH_NW(BN_, V_, __bf16);              \
-    else if (d.out_dtype == CLSKD_F16) LAUNCH_NW(BN_, V_, _Float16);        \
-    else LAUNCH_NW(BN_, V_, float);                                         \
-  } while (0)
-  if (d.N <= 32) {
-    if (d.vec4) LAUNCH_O(32, true); else LAUNCH_O(32, false);
-  } else if (d.N <= 64) {
-    if (d.vec4) LAUNCH_O(64, true); else LAUNCH_O(64, false);
-  } else {
-    if (d.vec4) LAUNCH_O(128, true); else LAUNCH_O(128, false);
-  }
-#undef LAUNCH_O
-#undef LAUNCH_NW
-#undef LAUNCH
-  CLSKD_LAUNCH_CHECK("conv2d");
   return CLSKD_OK;
 }

@@ -21,7 +21,7 @@
 // (pointwise_ok) and everything else runs the engines.
 #include <stdlib.h>
 
-#include "common.h"
+#include "conv_dispatch.h"
 
 namespace clskd {
 
@@ -199,14 +199,11 @@ static void launch_pw_c(const clskd_conv_desc& d, hipStream_t st) {
   }
 }
 
-bool conv_pointwise_takes(const clskd_conv_desc& d) { return pointwise_ok(d); }
-
-int launch_conv_pointwise(const clskd_conv_desc& d, hipStream_t st, bool* launched) {
-  *launched = false;
-  if (!pointwise_ok(d)) return CLSKD_OK;
-  if (d.N == 64) launch_pw_c<64>(d, st);
-  else launch_pw_c<32>(d, st);
-  *launched = true;
+int conv_pointwise(const clskd_conv_desc& d, const hipStream_t* st, bool* took) {
+  *took = pointwise_ok(d);
+  if (!*took || !st) return CLSKD_OK;
+  if (d.N == 64) launch_pw_c<64>(d, *st);
+  else launch_pw_c<32>(d, *st);
   return CLSKD_OK;
 }
 

@@ -29,7 +29,7 @@
 #include <stdlib.h>
 
 #include "bnfold.h"
-#include "common.h"
+#include "conv_dispatch.h"
 
 namespace clskd {
 
@@ -440,12 +440,7 @@ static bool split_plan(const clskd_conv_desc& d, SplitArgs& a, int& nt, int& bk,
   bk = d.K % 64 == 0 ? 64 : d.K % 32 == 0 ? 32 : 16;
   const int cap_bk = knob(KNOB_SPLIT_BK);  // A/B: the deepest K-tile allowed (0: 64)
   if (cap_bk == 16 || cap_bk == 32) bk = bk < cap_bk ? bk : cap_bk;
-  a.kt_taps = 1;
-  a.kt_cpt = d.K / bk;
-  if (d.ntaps > 1 && d.ctot % bk == 0 && (int64_t)d.ntaps * d.ctot == d.K) {
-    a.kt_taps = d.ntaps;
-    a.kt_cpt = d.ctot / bk;
-  }
+  conv_k_order(d, bk, false, a.kt_taps, a.kt_cpt);
   a.f = make_bnfold(d);
   const int ncu = device_cu_count();
   // 4-wave workgroups, as many per CU as LDS holds (up to three): more waves per SIMD hide more
@@ -465,21 +460,13 @@ static bool split_plan(const clskd_conv_desc& d, SplitArgs& a, int& nt, int& bk,
   return true;
 }
 
-// force: the descriptor asked for split products (CLSKD_F32X3, passed here as CLSKD_F32);
-// otherwise the global A/B knob CLSKD_F32_SPLIT routes every fp32 descriptor
-bool conv_split3_takes(const clskd_conv_desc& d, bool force) {
-  if (!force && knob(KNOB_F32_SPLIT) != 1) return false;
-  SplitArgs a;
-  int nt = 0, bk = 0, grid = 0;
-  return split_plan(d, a, nt, bk, grid);
-}
-
-int launch_conv_split3(const clskd_conv_desc& d, hipStream_t st, bool* launched, bool force) {
-  *launched = false;
-  if (!force && knob(KNOB_F32_SPLIT) != 1) return CLSKD_OK;
+// (Which descriptors are offered: the dispatch table's gate, conv_igemm.hip.)
+int conv_split3(const clskd_conv_desc& d, const hipStream_t* stp, bool* took) {
   SplitArgs a;
   int nt = 0, bk = 0, grid = 0, cus = 0;
-  if (!split_plan(d, a, nt, bk, grid, &cus)) return CLSKD_OK;
+  *took = split_plan(d, a, nt, bk, grid, &cus);
+  if (!*took || !stp) return CLSKD_OK;
+  const hipStream_t st = *stp;
   // CLSKD_SPLIT_OCC=1 (default): the grid holds only the workgroups the instance's register
   // occupancy keeps resident (the plan counts LDS only: up to 3 per CU, while 208-404 VGPRs allow
   // 1-2), so every workgroup is resident from the start and walks its tiles as one persistent
@@ -535,7 +522,6 @@ int launch_conv_split3(const clskd_conv_desc& d, hipStream_t st, bool* launched,
     else SP3(4, 16, 2);
   }
 #undef SP3
-  *launched = true;
   return CLSKD_OK;
 }
 

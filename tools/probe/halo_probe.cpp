@@ -35,12 +35,13 @@ int main() {
   d.ntaps = 9; d.ctot = C; d.seg_c[0] = C;
   for (int t = 0; t < 9; ++t) { d.tap_df[t] = t / 3 - 1; d.tap_dt[t] = t % 3 - 1; }
   bool launched = false;
-  for (int rep = 0; rep < 3; ++rep) clskd::launch_conv_halo(d, 0, &launched);
+  const hipStream_t st = 0;
+  for (int rep = 0; rep < 3; ++rep) clskd::conv_halo(d, &st, &launched);
   (void)hipDeviceSynchronize();
   hipEvent_t e0, e1;
   (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
   (void)hipEventRecord(e0, 0);
-  clskd::launch_conv_halo(d, 0, &launched);
+  clskd::conv_halo(d, &st, &launched);
   (void)hipEventRecord(e1, 0);
   (void)hipDeviceSynchronize();
   float ms; (void)hipEventElapsedTime(&ms, e0, e1);
