@@ -586,6 +586,49 @@ int clskd_bn_bwd(const void* x, const float* dy, int64_t rows, int32_t C, const 
                  float* dgamma, float* dbeta, float* dalpha, float* dx, int32_t accumulate_dx,
                  int32_t accumulate_params, int32_t dtype, void* stream);
 
+/* ComplexBatchNorm [+ PReLU] (tools_for_model.py:335-508; DCCRN.py:80,123 with use_cbn=True)
+ * over a fp32 BFTC tensor x[rows][C]: complex channel c of Cc = C/2 has its real part at column
+ * c and its imaginary part at column Cc + c.  C a multiple of 8, C <= 2048; x, y, dy, dx, coef,
+ * stats and work 16-byte aligned.  No entry allocates or synchronises.
+ *   coef  [6][Cc] fp32: Zrr Zri Zir Zii Sr Si, y = Z x + S with Z = W V^-1/2 and S = B - Z M
+ *         (tools_for_model.py:491-505)
+ *   stats [8][Cc] fp32 (optional in the forward, the backward's input): Mr Mi, Vrr Vri Vii with
+ *         eps added, Urr Uri Uii = V^-1/2 (tools_for_model.py:462-480)
+ *   clskd_cbn_stats_partial: per-block fp64 sums {r, i, r^2, i^2, r*i} -> partial[nblk][Cc][5]
+ *         (tools_for_model.py:427-453), nblk = clskd_cbn_stats_blocks(rows, C)
+ *   clskd_cbn_finalize: fixed-order sum of the partials, biased moments in fp64, the running
+ *         buffers lerped n_updates times with the moments before eps (tools_for_model.py:433-457;
+ *         all five pointers or none), then coef / stats
+ *   clskd_cbn_eval_coeffs: coef / stats from the running buffers (tools_for_model.py:435-461)
+ *   clskd_cbn_apply: y = Z x + S (tools_for_model.py:500-507), then PReLU(alpha[0]) if alpha;
+ *         y may be x */
+int32_t clskd_cbn_stats_blocks(int64_t rows, int32_t C);
+int clskd_cbn_stats_partial(const float* x, int64_t rows, int32_t C, double* partial,
+                            int32_t nblk, void* stream);
+int clskd_cbn_finalize(const double* partial, int32_t nblk, int64_t rows, int32_t C,
+                       const float* Wrr, const float* Wri, const float* Wii, const float* Br,
+                       const float* Bi, float eps, float* RMr, float* RMi, float* RVrr,
+                       float* RVri, float* RVii, float momentum, int32_t n_updates, float* coef,
+                       float* stats, void* stream);
+int clskd_cbn_eval_coeffs(const float* RMr, const float* RMi, const float* RVrr,
+                          const float* RVri, const float* RVii, const float* Wrr,
+                          const float* Wri, const float* Wii, const float* Br, const float* Bi,
+                          float eps, int32_t C, float* coef, float* stats, void* stream);
+int clskd_cbn_apply(const float* x, float* y, int64_t rows, int32_t C, const float* coef,
+                    const float* alpha, void* stream);
+/* ComplexBatchNorm(train) [+ PReLU] backward (the autograd of tools_for_model.py:398-508) in the
+ * three-kernel shape of clskd_bn_bwd: x the RAW conv output, dy = dL/d(output), coef / stats the
+ * forward's tables.  Writes dWrr dWri dWii dBr dBi dalpha (accumulate_params) and
+ * dx = A dy' + K x + k per complex channel (accumulate_dx; dx NULL: parameters only), fp32.
+ * `work`: clskd_cbn_bwd_workspace(nblk, C) doubles, nblk = clskd_cbn_bwd_blocks(rows, C). */
+int32_t clskd_cbn_bwd_blocks(int64_t rows, int32_t C);
+int64_t clskd_cbn_bwd_workspace(int32_t nblk, int32_t C);
+int clskd_cbn_bwd(const float* x, const float* dy, int64_t rows, int32_t C, const float* coef,
+                  const float* stats, const float* Wrr, const float* Wri, const float* Wii,
+                  const float* alpha, double* work, int32_t nblk, float* dWrr, float* dWri,
+                  float* dWii, float* dBr, float* dBi, float* dalpha, float* dx,
+                  int32_t accumulate_dx, int32_t accumulate_params, void* stream);
+
 /* ABF fusion backward (framework.py:209-219): from dout = dL/d(fused x), dx = dL/d(conv1 BN
  * output) and dyup = dL/d(upsampled residual) ([B][F][T][64]); operands as clskd_abf_fuse.
  * grad_dtype (CLSKD_F32 or CLSKD_BF16) is the storage type of all four gradient maps (dout,

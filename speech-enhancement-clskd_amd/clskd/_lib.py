@@ -170,6 +170,17 @@ SIGNATURES = {
     "clskd_bn_eval_coeffs": (_i32, [_p, _p, _p, _p, _f32, _i32, _p, _p, _p]),
     "clskd_bn_apply": (_i32, [_p, _p, _i64, _i32, _p, _p, _p, _i32, _p]),
     "clskd_bn_apply_reim": (_i32, [_p, _p, _i64, _i32, _p, _p, _p, _i32, _p]),
+    "clskd_cbn_stats_blocks": (_i32, [_i64, _i32]),
+    "clskd_cbn_stats_partial": (_i32, [_p, _i64, _i32, _p, _i32, _p]),
+    "clskd_cbn_finalize": (_i32, [_p, _i32, _i64, _i32, _p, _p, _p, _p, _p, _f32, _p, _p, _p, _p,
+                                  _p, _f32, _i32, _p, _p, _p]),
+    "clskd_cbn_eval_coeffs": (_i32, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _f32, _i32, _p, _p,
+                                     _p]),
+    "clskd_cbn_apply": (_i32, [_p, _p, _i64, _i32, _p, _p, _p]),
+    "clskd_cbn_bwd_blocks": (_i32, [_i64, _i32]),
+    "clskd_cbn_bwd_workspace": (_i64, [_i32, _i32]),
+    "clskd_cbn_bwd": (_i32, [_p, _p, _i64, _i32, _p, _p, _p, _p, _p, _p, _p, _i32, _p, _p, _p, _p,
+                             _p, _p, _p, _i32, _i32, _p]),
     "clskd_mask_bdt": (_i32, [_p, _i32, _p, _i32, _i32, _i32, _p, _i32, _p]),
     "clskd_lstm_recurrent": (_i32, [_p, _i64, _i64, _i64, _p, _i32, _i32, _i32, _i32, _p, _i64,
                                     _i64, _i64, _p]),

@@ -321,8 +321,17 @@ def _dec_pack_fn(taps_kf):
     return fn
 
 
+def _cbn_bwd(raw, dy, coef, stats, cbn, pr, draw, pg, acc):
+    """ComplexBatchNorm + PReLU backward of one taped layer (the tape entry of DCCRN._cnorm):
+    d raw, and the five parameter gradients and dalpha scattered straight into pg."""
+    ops.cbn_bwd(raw, dy, coef, stats, cbn, pr.weight, draw, pg.get(cbn.Wrr), pg.get(cbn.Wri),
+                pg.get(cbn.Wii), pg.get(cbn.Br), pg.get(cbn.Bi), pg.get(pr.weight),
+                accumulate_params=acc)
+
+
 def dccrn_backward(m, tape, enc, dec, dec_in, lstm_io, g, pg, acc_params=False, join=None):
-    """Reverse of DCCRN.run for a student `m` (fp32 activations).
+    """Reverse of DCCRN.run for a student `m` (fp32 activations; BatchNorm or, with
+    m.use_cbn, ComplexBatchNorm layers).
     tape: the forward tape; enc/dec/dec_in/lstm_io: the forward's activations.
     g: upstream gradient buffers (fp32): g['wav'] [B][L] or None; g['enc'][i] like enc[i];
        g['dec'][k] (k < 5) like dec[k]; g['dec_in'] like dec_in.  Consumed (accumulated into).
@@ -396,9 +405,12 @@ def dccrn_backward(m, tape, enc, dec, dec_in, lstm_io, g, pg, acc_params=False, 
             raw, coef, mv = tape["dec_bn"][d]
             bn, pr = mod[1], mod[2]
             draw = _empty(raw.shape, dev)
-            ops.bn_bwd(raw, g["dec"][d], coef[:Co], coef[Co:], mv[0], mv[1], bn.eps, bn.weight,
-                       pr.weight, draw, pg.get(bn.weight), pg.get(bn.bias), pg.get(pr.weight),
-                       accumulate_params=acc_params)
+            if m.use_cbn:
+                _cbn_bwd(raw, g["dec"][d], coef, mv, bn, pr, draw, pg, acc_params)
+            else:
+                ops.bn_bwd(raw, g["dec"][d], coef[:Co], coef[Co:], mv[0], mv[1], bn.eps,
+                           bn.weight, pr.weight, draw, pg.get(bn.weight), pg.get(bn.bias),
+                           pg.get(pr.weight), accumulate_params=acc_params)
         segs = [seg_bftc(out_t, 0, Cof, out_t0, T), seg_bftc(skip, 0, Csk)]
         # weight gradients: both polyphase parities into one concatenated packed buffer
         packs = [m._dec_w(d, p, "fp32") for p in (0, 1)]
@@ -541,9 +553,12 @@ def dccrn_backward(m, tape, enc, dec, dec_in, lstm_io, g, pg, acc_params=False, 
         Co = raw.shape[-1]
         Fo = raw.shape[1]
         draw = _empty(raw.shape, dev)
-        ops.bn_bwd(raw, g["enc"][i], coef[:Co], coef[Co:], mv[0], mv[1], bn.eps, bn.weight,
-                   pr.weight, draw, pg.get(bn.weight), pg.get(bn.bias), pg.get(pr.weight),
-                   accumulate_params=acc_params)
+        if m.use_cbn:
+            _cbn_bwd(raw, g["enc"][i], coef, mv, bn, pr, draw, pg, acc_params)
+        else:
+            ops.bn_bwd(raw, g["enc"][i], coef[:Co], coef[Co:], mv[0], mv[1], bn.eps, bn.weight,
+                       pr.weight, draw, pg.get(bn.weight), pg.get(bn.bias), pg.get(pr.weight),
+                       accumulate_params=acc_params)
         src = tape["spec_b"] if i == 0 else enc[i - 1]
         Ci = src.shape[-1]
         wp, _ = m._enc_w(i, "fp32")

@@ -49,8 +49,23 @@ def n_frames(num_samples, win=win_len, hop=win_inc):
     return (num_samples + 2 * (win - hop) - win) // hop + 1
 
 
-def dccrn_param_shapes(rnn_units, kernel_num, rnn_layers=2, ksize=5, fft=fft_len):
-    """Ordered {state_dict key: shape} of the reference DCCRN (use_clstm=True, use_cbn=False)."""
+CBN_LEAVES = ("Wrr", "Wri", "Wii", "Br", "Bi", "RMr", "RMi", "RVrr", "RVri", "RVii")
+
+
+def _norm_shapes(s, p, channels, use_cbn):
+    """The normalisation layer's leaves in registration order: nn.BatchNorm2d, or ComplexBatchNorm
+    (tools_for_model.py:347-366: every leaf has channels // 2 entries)."""
+    if use_cbn:
+        for k in CBN_LEAVES:
+            s[p + k] = (channels // 2,)
+    else:
+        for k in ("weight", "bias", "running_mean", "running_var"):
+            s[p + k] = (channels,)
+    s[p + "num_batches_tracked"] = ()
+
+
+def dccrn_param_shapes(rnn_units, kernel_num, rnn_layers=2, ksize=5, fft=fft_len, use_cbn=False):
+    """Ordered {state_dict key: shape} of the reference DCCRN (use_clstm=True; use_cbn as given)."""
     kn = [2] + list(kernel_num)
     s = OrderedDict()
     for i in range(len(kn) - 1):
@@ -59,9 +74,7 @@ def dccrn_param_shapes(rnn_units, kernel_num, rnn_layers=2, ksize=5, fft=fft_len
         for part in ("real_conv", "imag_conv"):
             s[p + f"0.{part}.weight"] = (cout, cin, ksize, 2)
             s[p + f"0.{part}.bias"] = (cout,)
-        for k in ("weight", "bias", "running_mean", "running_var"):
-            s[p + f"1.{k}"] = (kn[i + 1],)
-        s[p + "1.num_batches_tracked"] = ()
+        _norm_shapes(s, p + "1.", kn[i + 1], use_cbn)
         s[p + "2.weight"] = (1,)
     hidden_dim = fft // (2 ** len(kn))
     feat = hidden_dim * kn[-1]
@@ -86,9 +99,7 @@ def dccrn_param_shapes(rnn_units, kernel_num, rnn_layers=2, ksize=5, fft=fft_len
             s[p + f"0.{part}.weight"] = (cin, cout, ksize, 2)  # ConvTranspose2d: [in, out, kh, kw]
             s[p + f"0.{part}.bias"] = (cout,)
         if idx != 1:
-            for k in ("weight", "bias", "running_mean", "running_var"):
-                s[p + f"1.{k}"] = (kn[idx - 1],)
-            s[p + "1.num_batches_tracked"] = ()
+            _norm_shapes(s, p + "1.", kn[idx - 1], use_cbn)
             s[p + "2.weight"] = (1,)
     s.update(enh)
     return s

@@ -27,7 +27,7 @@ import torch.nn as nn
 from . import config as cfg
 from . import _lib, ops
 from .framework import MultiResolutionSTFTLoss, SPKDLoss, build_review_kd
-from .model import DCCRN
+from .model import DCCRN, refuse_cbn
 
 
 _SIDE = {}
@@ -174,6 +174,8 @@ class KnowledgeDistillation(nn.Module):
     def __init__(self, teacher, student, sftf_loss=MultiResolutionSTFTLoss, spkd_loss=SPKDLoss,
                  cfg=cfg, abf_reinit="step", precision="fp32"):
         super().__init__()
+        refuse_cbn(teacher, "KnowledgeDistillation")
+        refuse_cbn(student, "KnowledgeDistillation")
         self.automatic_optimization = True
         self.teacher = teacher
         for p in self.teacher.parameters():
@@ -578,6 +580,8 @@ class SPKDDistillation(nn.Module):
     def __init__(self, teacher, student, sftf_loss=MultiResolutionSTFTLoss, spkd_loss=SPKDLoss,
                  cfg=cfg, precision="fp32"):
         super().__init__()
+        refuse_cbn(teacher, "SPKDDistillation")
+        refuse_cbn(student, "SPKDDistillation")
         self.teacher = teacher
         for p in self.teacher.parameters():
             p.requires_grad = False

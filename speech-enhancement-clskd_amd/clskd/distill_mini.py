@@ -22,7 +22,7 @@ from .asteroid_backward import mini_backward
 from .backward import mrstft_backward
 from .distill import _validation_step
 from .framework import MultiResolutionSTFTLoss, SPKDLoss
-from .model import DCCRN
+from .model import DCCRN, refuse_cbn
 
 KD_KINDS = ("spkd", "mse", "stft")
 
@@ -46,6 +46,7 @@ class OutputDistillation(nn.Module):
     def __init__(self, teacher, student, kd="spkd", sftf_loss=MultiResolutionSTFTLoss,
                  spkd_loss=SPKDLoss, cfg=cfg):
         super().__init__()
+        refuse_cbn(teacher, "OutputDistillation")
         if kd not in KD_KINDS:
             raise ValueError(f"kd must be one of {KD_KINDS}, got {kd!r}")
         if not isinstance(student, DCCRNet_mini):

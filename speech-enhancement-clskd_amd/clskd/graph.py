@@ -23,6 +23,7 @@ import torch
 
 from . import ops
 from .distill import KnowledgeDistillation
+from .model import refuse_cbn
 
 
 def _bn_buffers(kd):
@@ -41,6 +42,8 @@ class StepGraph:
         if not isinstance(kd, (KnowledgeDistillation, SPKDDistillation)):
             raise TypeError("StepGraph captures a clskd.distill.KnowledgeDistillation (C2) or "
                             "SPKDDistillation (C4) step")
+        for m in (kd.teacher, kd.student):
+            refuse_cbn(m, "a captured step graph")
         if not X.is_cuda:
             raise RuntimeError("StepGraph needs device-resident inputs")
         self.kd = kd

@@ -7,7 +7,9 @@ nn.LSTM, …) are parameter containers only: ``DCCRN.forward`` runs the whole ne
 libclskd_hip.so on BFTC ([batch][freq][time][channel]) buffers, never through torch compute.
 
 Supported configuration = the one the reference trains and distils: masking_mode 'E',
-use_clstm=True, use_cbn=False, kernel_size 5, fft 512 / win 400 / hop 100.  Anything else raises.
+use_clstm=True, kernel_size 5, fft 512 / win 400 / hop 100, with either normalisation the
+reference offers: nn.BatchNorm2d (use_cbn=False) or ComplexBatchNorm (use_cbn=True, fp32
+activations; forward, taps, DCCRN.loss and SupervisedTraining).  Anything else raises.
 """
 import os
 import weakref
@@ -143,6 +145,65 @@ class NavieComplexLSTM(nn.Module):
 
     def forward(self, x):
         raise NotImplementedError("NavieComplexLSTM runs inside DCCRN.forward (HIP executor)")
+
+
+class ComplexBatchNorm(nn.Module):
+    """Parameter container for tools_for_model.py:335-396: Wrr, Wri, Wii, Br, Bi and the buffers
+    RMr, RMi, RVrr, RVri, RVii, num_batches_tracked, each of num_features // 2 complex channels.
+    The layer itself runs inside DCCRN.forward (csrc/cbn.hip through ops.cbn_forward)."""
+
+    def __init__(self, num_features, eps=1e-5, momentum=0.1, affine=True,
+                 track_running_stats=True, complex_axis=1):
+        super().__init__()
+        self.num_features = num_features // 2
+        self.eps, self.momentum, self.affine = eps, momentum, affine
+        self.track_running_stats = track_running_stats
+        self.complex_axis = complex_axis
+        for name in ("Wrr", "Wri", "Wii", "Br", "Bi"):
+            if affine:
+                setattr(self, name, nn.Parameter(torch.empty(self.num_features)))
+            else:
+                self.register_parameter(name, None)
+        if track_running_stats:
+            for name, one in (("RMr", 0), ("RMi", 0), ("RVrr", 1), ("RVri", 0), ("RVii", 1)):
+                self.register_buffer(name, torch.full((self.num_features,), float(one)))
+            self.register_buffer("num_batches_tracked", torch.tensor(0, dtype=torch.long))
+        else:
+            for name in ("RMr", "RMi", "RVrr", "RVri", "RVii", "num_batches_tracked"):
+                self.register_parameter(name, None)
+        self.reset_parameters()
+
+    def reset_running_stats(self):
+        if self.track_running_stats:
+            self.RMr.zero_()
+            self.RMi.zero_()
+            self.RVrr.fill_(1)
+            self.RVri.zero_()
+            self.RVii.fill_(1)
+            self.num_batches_tracked.zero_()
+
+    def reset_parameters(self):
+        self.reset_running_stats()
+        if self.affine:
+            self.Br.data.zero_()
+            self.Bi.data.zero_()
+            self.Wrr.data.fill_(1)
+            self.Wri.data.uniform_(-.9, +.9)  # W stays positive definite
+            self.Wii.data.fill_(1)
+
+    def forward(self, x):
+        raise NotImplementedError("ComplexBatchNorm runs inside DCCRN.forward (HIP executor)")
+
+    def extra_repr(self):
+        return (f"{self.num_features}, eps={self.eps}, momentum={self.momentum}, "
+                f"affine={self.affine}, track_running_stats={self.track_running_stats}")
+
+
+def refuse_cbn(model, who):
+    """Consumers that are built around nn.BatchNorm2d (fused statistics, folded applies, captured
+    steps) refuse a DCCRN(use_cbn=True) instead of treating its layers as BatchNorms."""
+    if getattr(model, "use_cbn", False):
+        raise NotImplementedError(f"{who} does not support a DCCRN built with use_cbn=True")
 
 
 def _pv(*tensors):
@@ -299,10 +360,10 @@ class DCCRN(nn.Module):
                  masking_mode="E", use_clstm=False, use_cbn=False, kernel_size=5,
                  kernel_num=[16, 32, 64, 128, 256, 256]):
         super().__init__()
-        if masking_mode != "E" or not use_clstm or use_cbn or kernel_size != 5:
+        if masking_mode != "E" or not use_clstm or kernel_size != 5:
             raise NotImplementedError(
                 "clskd.DCCRN builds the DCCRN-CL path of the reference (masking_mode='E', "
-                "use_clstm=True, use_cbn=False, kernel_size=5)")
+                "use_clstm=True, kernel_size=5; use_cbn False or True)")
         if (win_len, win_inc, fft_len) != (400, 100, 512):
             raise NotImplementedError("clskd.DCCRN is built for win 400 / hop 100 / fft 512")
         self.win_len, self.win_inc, self.fft_len, self.win_type = win_len, win_inc, fft_len, win_type
@@ -313,6 +374,8 @@ class DCCRN(nn.Module):
         self.kernel_num = [2] + list(kernel_num)
         self.masking_mode = masking_mode
         self.use_clstm = use_clstm
+        self.use_cbn = bool(use_cbn)
+        norm = ComplexBatchNorm if use_cbn else nn.BatchNorm2d  # DCCRN.py:80,123
         self.fix = True
         self.stft = ConvSTFT(win_len, win_inc, fft_len, win_type, "complex", fix=True)
         self.istft = ConviSTFT(win_len, win_inc, fft_len, win_type, "complex", fix=True)
@@ -323,7 +386,7 @@ class DCCRN(nn.Module):
             self.encoder.append(nn.Sequential(
                 ComplexConv2d(kn[idx], kn[idx + 1], kernel_size=(kernel_size, 2), stride=(2, 1),
                               padding=(2, 1)),
-                nn.BatchNorm2d(kn[idx + 1]),
+                norm(kn[idx + 1]),
                 nn.PReLU()))
         hidden_dim = fft_len // (2 ** len(kn))
         rnns = []
@@ -337,7 +400,7 @@ class DCCRN(nn.Module):
             mods = [ComplexConvTranspose2d(kn[idx] * 2, kn[idx - 1], kernel_size=(kernel_size, 2),
                                            stride=(2, 1), padding=(2, 0), output_padding=(1, 0))]
             if idx != 1:
-                mods += [nn.BatchNorm2d(kn[idx - 1]), nn.PReLU()]
+                mods += [norm(kn[idx - 1]), nn.PReLU()]
             self.decoder.append(nn.Sequential(*mods))
         self._wcache = {}
         self._pmaps = {}  # parameter group -> packing index map (_pack_group)
@@ -608,6 +671,21 @@ class DCCRN(nn.Module):
             return raw
         return ops.bn_apply(raw, raw, coef, pr.weight)
 
+    @staticmethod
+    def _cnorm(raw, cbn, pr, train, bn_updates, tape, key):
+        """ComplexBatchNorm + PReLU of a whole conv output (the _norm of a use_cbn model): one
+        statistics pass over the stored activation (train), the per-channel finalize, one apply
+        pass — in place unless a tape keeps the raw output with the coefficients and statistics
+        ops.cbn_bwd needs.  Returns the normalised tensor."""
+        if train and bn_updates > 0 and cbn.num_batches_tracked is not None:
+            cbn.num_batches_tracked += bn_updates
+        if tape is not None:
+            post, coef, stats = ops.cbn_forward(raw, torch.empty_like(raw), cbn, train, bn_updates,
+                                                alpha=pr.weight, return_coef=True)
+            tape.setdefault(key, []).append((raw, coef, stats))
+            return post
+        return ops.cbn_forward(raw, raw, cbn, train, bn_updates, alpha=pr.weight)
+
     def run(self, x, train=True, bn_updates=1, spec=None, want_masks=True, on_encoder=None,
             tape=None, taps_only=False, mark=None, on_decoder_tap=None, gram_taps=None):
         """See _run.  compute 'f32x3' (the student in precision 'mixed'): the fp32 convs of a
@@ -639,6 +717,15 @@ class DCCRN(nn.Module):
         BatchNorm + PReLU apply pass is fused with its SPKD Gram partials (ops.bn_apply_gram),
         so the step never reads the tap again for its Gram."""
         fuse_gram = gram_taps is not None and train and tape is None
+        cbn = self.use_cbn
+        if cbn and gram_taps is not None:
+            raise NotImplementedError("gram_taps (the fused BatchNorm-apply + Gram path) does not "
+                                      "support use_cbn=True")
+        if cbn and self.act_dtype != torch.float32:
+            raise NotImplementedError("use_cbn=True needs fp32 activations (compute 'fp32' or "
+                                      f"'f32x3'), not compute={self.compute!r}")
+        if cbn and torch.cuda.is_current_stream_capturing():
+            raise NotImplementedError("a captured step graph does not support use_cbn=True")
         if not x.is_cuda:
             raise RuntimeError("clskd.DCCRN.forward needs inputs on the HIP device")
         x = x.float()
@@ -673,7 +760,13 @@ class DCCRN(nn.Module):
             taps = [(kf - 2, kt - 1) for kf in range(5) for kt in range(2)]
             raw = torch.empty(B, Fo, T, Co, **act)
             _, bn, pr = self._layer_refs()["enc"][i]
-            mv = torch.empty(2, Co, **f32) if tape is not None else None
+            mv = torch.empty(2, Co, **f32) if (tape is not None and not cbn) else None
+            if cbn:  # the five complex moments are not fused into the conv epilogue
+                ops.conv(segs, taps, B, Fo, T, Co, wp, bias, raw, OutMap(Fo * T * Co, T * Co, Co),
+                         stride_f=2)
+                enc.append(self._cnorm(raw, bn, pr, train, bn_updates, tape, "enc_bn"))
+                F = Fo
+                continue
             st = (ops.BnStats(bn, Co, B * Fo * T, bn_updates, dev,
                               stats_out=(mv[0], mv[1]) if mv is not None else None)
                   if train else None)
@@ -767,8 +860,9 @@ class DCCRN(nn.Module):
             bn = pr = mv = st = None
             if has_bn:
                 bn, pr = dbn, dpr
-                mv = torch.empty(2, Co, **f32) if tape is not None else None
-                if train:  # one BatchNorm over both polyphase parities (2 x B*F*(T+1) rows)
+                mv = torch.empty(2, Co, **f32) if (tape is not None and not cbn) else None
+                # one BatchNorm over both polyphase parities (2 x B*F*(T+1) rows)
+                if train and not cbn:
                     st = ops.BnStats(bn, Co, 2 * B * F * (T + 1), bn_updates, dev,
                                      stats_out=(mv[0], mv[1]) if mv is not None else None)
             launches = []
@@ -782,7 +876,9 @@ class DCCRN(nn.Module):
                 st.partials_only()  # the parities dispatch to different kernels: no fold
             for parity, a in enumerate(launches):
                 ops.conv(*a, bn_stats=(st, parity == 1) if st is not None else None)
-            if has_bn:
+            if has_bn and cbn:  # both parities as one layer, after both conv launches
+                raw = self._cnorm(raw, bn, pr, train, bn_updates, tape, "dec_bn")
+            elif has_bn:
                 raw = self._norm(raw, bn, pr, st, train, bn_updates, tape, "dec_bn", mv,
                                  gram_taps if (fuse_gram and d < nl - 1) else None, B)
             elif tape is not None:

@@ -878,6 +878,83 @@ def bn_apply(x, y, coef, alpha=None):
 
 
 # ------------------------------------------------------------------------------------------
+# ComplexBatchNorm (+ PReLU): csrc/cbn.hip
+# ------------------------------------------------------------------------------------------
+def _cbn_check(x, what):
+    if x.dtype != torch.float32 or not x.is_contiguous():
+        raise RuntimeError(f"{what}: ComplexBatchNorm runs on contiguous fp32 BFTC activations")
+    Cn = x.shape[-1]
+    if Cn % 8 or Cn > 2048:
+        raise RuntimeError(f"{what}: C={Cn} must be a multiple of 8, at most 2048")
+    return Cn, x.numel() // Cn
+
+
+def cbn_forward(x, y, cbn, train, n_updates=1, alpha=None, return_coef=False):
+    """ComplexBatchNorm (model.ComplexBatchNorm parameters / buffers `cbn`) over a fp32 BFTC
+    tensor whose last axis is [re | im], then optional PReLU (single alpha).
+    train: batch statistics, the five running buffers lerped n_updates times (the meaning
+    BnStats gives n_updates; num_batches_tracked is the caller's); else the running buffers.
+    y=None: coefficients only.  return_coef: (y, coef [6][Cc], stats [8][Cc]) — what cbn_apply and
+    cbn_bwd take."""
+    L = lib()
+    Cn, rows = _cbn_check(x, "cbn_forward")
+    Cc = Cn // 2
+    dev = x.device
+    st = _stream()
+    coef = torch.empty(6, Cc, device=dev, dtype=torch.float32)
+    stats = torch.empty(8, Cc, device=dev, dtype=torch.float32) if return_coef else None
+    w = (ptr(cbn.Wrr), ptr(cbn.Wri), ptr(cbn.Wii), ptr(cbn.Br), ptr(cbn.Bi))
+    run = (cbn.RMr, cbn.RMi, cbn.RVrr, cbn.RVri, cbn.RVii)
+    if train:
+        nblk = int(L.clskd_cbn_stats_blocks(rows, Cn))
+        part = torch.empty(nblk * Cc * 5, device=dev, dtype=torch.float64)
+        check(L.clskd_cbn_stats_partial(ptr(x), rows, Cn, ptr(part), nblk, st), "cbn_stats")
+        upd = n_updates > 0 and all(r is not None for r in run)
+        rp = tuple(ptr(r) for r in run) if upd else (None,) * 5
+        check(L.clskd_cbn_finalize(ptr(part), nblk, rows, Cn, *w, cbn.eps, *rp, cbn.momentum,
+                                   n_updates if upd else 0, ptr(coef), ptr(stats), st),
+              "cbn_finalize")
+    else:
+        if any(r is None for r in run):
+            raise RuntimeError("cbn_forward: eval mode needs the running buffers")
+        check(L.clskd_cbn_eval_coeffs(*(ptr(r) for r in run), *w, cbn.eps, Cn, ptr(coef),
+                                      ptr(stats), st), "cbn_eval")
+    if y is not None:
+        cbn_apply(x, y, coef, alpha)
+    if return_coef:
+        return y, coef, stats
+    return coef if y is None else y
+
+
+def cbn_apply(x, y, coef, alpha=None):
+    """y = Z x + S per complex channel with cbn_forward's coef [then PReLU(alpha)]; y may be x."""
+    Cn, rows = _cbn_check(x, "cbn_apply")
+    assert y.dtype == x.dtype and y.shape == x.shape and y.is_contiguous()
+    assert coef.numel() == 3 * Cn
+    check(lib().clskd_cbn_apply(ptr(x), ptr(y), rows, Cn, ptr(coef), ptr(alpha), _stream()),
+          "cbn_apply")
+    return y
+
+
+def cbn_bwd(x, dy, coef, stats, cbn, alpha, dx, dWrr=None, dWri=None, dWii=None, dBr=None,
+            dBi=None, dalpha=None, accumulate_dx=False, accumulate_params=False):
+    """ComplexBatchNorm(train) [+ PReLU] backward over the raw fp32 BFTC x with the forward's
+    coef / stats (cbn_forward(..., return_coef=True)); dx=None: parameter gradients only."""
+    L = lib()
+    Cn, rows = _cbn_check(x, "cbn_bwd")
+    assert dy.dtype == torch.float32 and dy.shape == x.shape and dy.is_contiguous()
+    assert coef.numel() == 3 * Cn and stats.numel() == 4 * Cn
+    nblk = int(L.clskd_cbn_bwd_blocks(rows, Cn))
+    work = torch.empty(int(L.clskd_cbn_bwd_workspace(nblk, Cn)), dtype=torch.float64,
+                       device=x.device)
+    check(L.clskd_cbn_bwd(ptr(x), ptr(dy), rows, Cn, ptr(coef), ptr(stats), ptr(cbn.Wrr),
+                          ptr(cbn.Wri), ptr(cbn.Wii), ptr(alpha), ptr(work), nblk, ptr(dWrr),
+                          ptr(dWri), ptr(dWii), ptr(dBr), ptr(dBi), ptr(dalpha), ptr(dx),
+                          int(accumulate_dx), int(accumulate_params), _stream()), "cbn_bwd")
+    return dx
+
+
+# ------------------------------------------------------------------------------------------
 # LSTM, STFT helpers, ABF fuse
 # ------------------------------------------------------------------------------------------
 def lstm_recurrent(gx, gx_ws, gx_seq, gx_t, whh, nws, nseq, T, H, out, o_ws, o_seq, o_t):

@@ -25,6 +25,7 @@ import torch
 
 from . import config as cfg
 from . import ops
+from .model import refuse_cbn
 from .ops import OutMap, Seg, SegGeom
 
 HOP, WIN = 100, 400
@@ -48,6 +49,7 @@ class StreamingDCCRN:
     returns the offline-aligned [B][L] output (equal to model.eval()(x) up to fp32 rounding)."""
 
     def __init__(self, model, batch, graph=True):
+        refuse_cbn(model, "StreamingDCCRN")
         if model.training:
             raise ValueError("StreamingDCCRN runs eval-mode BatchNorm: call model.eval() first")
         self.m = model

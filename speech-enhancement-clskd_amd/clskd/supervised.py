@@ -69,7 +69,8 @@ class SupervisedTraining(nn.Module):
     ``KnowledgeDistillation`` / ``OutputDistillation`` without a teacher.
 
     model: a ``clskd.DCCRN`` in the student configuration (config.kernel_num_student,
-    rnn_units_student) or a ``DCCRNet_mini``.
+    rnn_units_student; ``use_cbn`` False or True: the taped forward and ``dccrn_backward`` route a
+    ComplexBatchNorm model through csrc/cbn.hip) or a ``DCCRNet_mini``.
     loss_mode: a DCCRN.loss mode (LOSS_MODES) or 'MRSTFT'.  For a DCCRNet_mini the LMS modes raise
     NotImplementedError (mini_backward has no entry point at the masked spectrum)."""
 

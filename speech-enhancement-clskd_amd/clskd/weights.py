@@ -13,6 +13,8 @@ which would hide bias and BN-affine bugs):
   * complex conv / convT weights  N(0, 0.05)   (the reference's init std, tools_for_model.py:231,260)
   * conv biases                   N(0, 0.02)
   * BN weight 1+0.1N, bias 0.1N, running_mean 0.1N, running_var 1+0.2U
+  * ComplexBatchNorm Wrr, Wii 1+0.1N; Wri U(-0.9, 0.9) (the reference's init); Br, Bi, RMr, RMi
+    0.1N; RVrr, RVii 1+0.2U; RVri 0.3(2U-1), so the running V stays positive definite
   * PReLU alpha 0.25 + 0.05N      (nn.PReLU init is 0.25)
   * LSTM / Linear                 U(-1/sqrt(fan), 1/sqrt(fan))   (torch defaults)
   * ABF conv1/conv2               U(-sqrt(3/fan_in), +)  == kaiming_uniform_(a=1) (framework.py:194-195)
@@ -57,6 +59,16 @@ def _value(seed, name, shape, shapes):
         return _f32(0.1 * g.standard_normal(shape))
     if leaf == "running_var":
         return _f32(1.0 + 0.2 * g.random(shape))
+    if leaf in ("Wrr", "Wii"):  # ComplexBatchNorm (tools_for_model.py:347-366)
+        return _f32(1.0 + 0.1 * g.standard_normal(shape))
+    if leaf == "Wri":
+        return _f32(g.uniform(-0.9, 0.9, shape))
+    if leaf in ("Br", "Bi", "RMr", "RMi"):
+        return _f32(0.1 * g.standard_normal(shape))
+    if leaf in ("RVrr", "RVii"):
+        return _f32(1.0 + 0.2 * g.random(shape))
+    if leaf == "RVri":
+        return _f32(0.3 * (2.0 * g.random(shape) - 1.0))
     if ".abfs." in name:
         return _abf_value(g, name, shape, shapes)
     if "_lstm." in name:  # nn.LSTM: U(-1/sqrt(H), 1/sqrt(H)), H = rows/4
