@@ -705,8 +705,8 @@ int clskd_complex_combine_bwd(const float* dreal, const float* dimag, int32_t B,
                               float* dh, void* stream);
 
 /* ------------------------------------------------------------------------------------------
- * Backward of the asteroid DCCRNet_mini training step (csrc/mini_bwd.hip; the rest of that
- * backward runs on the entries above).
+ * Backward of the asteroid DCCRNet_mini training step (csrc/mini_bwd.hip, and clskd_bn_bwd_reim
+ * beside clskd_bn_bwd in csrc/norm_bwd.hip; the rest of that backward runs on the entries above).
  * clskd_mask_bdt_bwd: reverse of clskd_mask_bdt (asteroid complex_nn.BoundComplexMask('tanh')
  *   then DCCRNet.apply_masks, oracle/asteroid_cpu.py:127-131).  dest = dL/d est [B][T][ldest]
  *   (re at f, im at 257 + f; the Nyquist columns 256 / 513 and the tail are ignored), spec as
@@ -718,8 +718,10 @@ int clskd_complex_combine_bwd(const float* dreal, const float* dimag, int32_t B,
  *   (oracle/asteroid_cpu.py:96-97, 120-121; forward clskd_bn_apply_reim) over fp32 BFTC
  *   x [rows][C]: slope alpha_re_im[0] on channels [0, C/2), alpha_re_im[1] on [C/2, C);
  *   dalpha_re_im[2] (optional) receives the two slope gradients, each a fixed-order fp64 sum over
- *   its half.  C a multiple of 4; work / nblk as clskd_bn_bwd (clskd_bn_bwd_workspace /
- *   clskd_bn_bwd_blocks); x, dy, dx, scale, shift, work 16-byte aligned.
+ *   its half.  The kernels are clskd_bn_bwd's, instantiated with the slope per half: with equal
+ *   slopes dx, dgamma and dbeta are clskd_bn_bwd's bit for bit.  C a multiple of 4; work / nblk as
+ *   clskd_bn_bwd (clskd_bn_bwd_workspace / clskd_bn_bwd_blocks); x, dy, dx, scale, shift, work
+ *   16-byte aligned.
  * clskd_mse_loss_grad: F.mse_loss(a, b, reduction='mean') (distill_MSE.py:85) and its gradient
  *   in one pass over two fp32 arrays of n elements: loss_out[0] (+)= scale * mean((a - b)^2)
  *   (fp64 block partials combined in a fixed order: bitwise repeatable), da (+)= scale * 2 (a - b)

@@ -2,7 +2,7 @@
 // DCCRN.py:80,123 with use_cbn=True).  A BFTC row of C = 2*Cc floats holds the real parts of the
 // Cc complex channels at [0, Cc) and the imaginary parts at [Cc, 2*Cc).  All passes are HBM-bound:
 // a thread owns one quad of complex channels (one 16-B load of reals, one of imaginaries per
-// row), statistics accumulate in fp64, reductions are two-level and fixed-order (no float
+// row), statistics accumulate in fp64, reductions are two-level and fixed-order (reduce.h: no float
 // atomics), per-channel algebra (V -> V^-1/2 -> Z, and its chain rule) runs in fp64 once per
 // channel.  fp32 activations only.
 //
@@ -10,92 +10,12 @@
 //   coef  [6]: Zrr Zri Zir Zii Sr Si        y = Z x + S   (S = B - Z M)
 //   stats [8]: Mr Mi Vrr Vri Vii Urr Uri Uii   (V with eps added, U = V^-1/2)
 #include "common.h"
+#include "reduce.h"
 
 namespace clskd {
 
 constexpr int CBN_NSTAT = 5;  // sum r, sum i, sum r^2, sum i^2, sum r*i
 constexpr int CBN_NBWD = 7;   // sum gr, gi, gr*xhr, gr*xhi, gi*xhr, gi*xhi, PReLU term
-
-// Block-level fixed-order sum of NQ quantities x 4 channels held by the (row lane, quad) threads:
-// out[(cg*4 + j) * NQ + k] = sum over the row lanes l < RP of acc[k][j], in two fixed-order levels:
-// G = min(16, RP) groups (group g sums lanes g, g + G, ... in that order, one thread per group and
-// quad), then the quad's first thread sums the groups.  With one quad per row (C = 8) a single
-// level would leave one thread walking 256 LDS rows per pass.  Two quantities per LDS pass
-// (red[256][9], the footprint of bn_stats_partial_kernel).
-template <int NQ>
-__device__ __forceinline__ void cbn_block_sum(const double (&acc)[NQ][4], int CG, int RP,
-                                              double* __restrict__ out) {
-  __shared__ double red[256][9];
-  const int tid = threadIdx.x;
-  const int G = RP < 16 ? RP : 16;
-  const int g = tid / CG, cgi = tid - g * CG;  // level-1 role of this thread (g < G)
-#pragma unroll
-  for (int k0 = 0; k0 < NQ; k0 += 2) {
-    const int k1 = k0 + 1 < NQ ? k0 + 1 : k0;  // odd NQ: the last pass carries one quantity
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      red[tid][j] = acc[k0][j];
-      red[tid][4 + j] = acc[k1][j];
-    }
-    __syncthreads();
-    double a[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    if (g < G) {
-      for (int l = g; l < RP; l += G) {
-        const int t = l * CG + cgi;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) a[j] += red[t][j];
-      }
-    }
-    __syncthreads();
-    if (g < G) {
-#pragma unroll
-      for (int j = 0; j < 8; ++j) red[tid][j] = a[j];  // row g * CG + cgi = tid
-    }
-    __syncthreads();
-    if (tid < CG) {
-      double b[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-      for (int l = 0; l < G; ++l) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) b[j] += red[l * CG + tid][j];
-      }
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        out[(tid * 4 + j) * NQ + k0] = b[j];
-        if (k0 + 1 < NQ) out[(tid * 4 + j) * NQ + k0 + 1] = b[4 + j];
-      }
-    }
-    __syncthreads();
-  }
-}
-
-// Sum partial[b][c][0..NQ) over b < nblk for channel c = blockIdx.x: strided per thread, then a
-// fixed LDS tree.  The result is valid in thread 0 (tot).
-template <int NQ>
-__device__ __forceinline__ void cbn_channel_sum(const double* __restrict__ partial, int nblk,
-                                                int Cc, int c, double (&tot)[NQ]) {
-  __shared__ double red[NQ][256];
-  const int tid = threadIdx.x;
-  double s[NQ];
-#pragma unroll
-  for (int k = 0; k < NQ; ++k) s[k] = 0.0;
-  for (int b = tid; b < nblk; b += 256) {
-    const double* p = partial + ((int64_t)b * Cc + c) * NQ;
-#pragma unroll
-    for (int k = 0; k < NQ; ++k) s[k] += p[k];
-  }
-#pragma unroll
-  for (int k = 0; k < NQ; ++k) red[k][tid] = s[k];
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (tid < o) {
-#pragma unroll
-      for (int k = 0; k < NQ; ++k) red[k][tid] += red[k][tid + o];
-    }
-    __syncthreads();
-  }
-#pragma unroll
-  for (int k = 0; k < NQ; ++k) tot[k] = red[k][0];
-}
 
 // V (eps already added) -> U = V^-1/2 by the closed form of the 2x2 square root
 // (tools_for_model.py:466-480): s = sqrt(det V), t = sqrt(tr V + 2s), U = adj(V + sI) / (s t).
@@ -145,19 +65,17 @@ __device__ __forceinline__ void cbn_channel_coeffs(int c, int Cc, double Mr, dou
   }
 }
 
-__device__ __forceinline__ f32x4 ldq(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
-
 // y = Z x + S of one quad (the one expression every pass uses, so the backward sees the PReLU
 // sign the forward saw)
 struct CbnCoef {
   f32x4 zrr, zri, zir, zii, sr, si;
   __device__ __forceinline__ void load(const float* coef, int Cc, int c0) {
-    zrr = ldq(coef + c0);
-    zri = ldq(coef + Cc + c0);
-    zir = ldq(coef + 2 * Cc + c0);
-    zii = ldq(coef + 3 * Cc + c0);
-    sr = ldq(coef + 4 * Cc + c0);
-    si = ldq(coef + 5 * Cc + c0);
+    zrr = load4<float>(coef + c0);
+    zri = load4<float>(coef + Cc + c0);
+    zir = load4<float>(coef + 2 * Cc + c0);
+    zii = load4<float>(coef + 3 * Cc + c0);
+    sr = load4<float>(coef + 4 * Cc + c0);
+    si = load4<float>(coef + 5 * Cc + c0);
   }
   __device__ __forceinline__ void y(const f32x4& xr, const f32x4& xi, f32x4& yr, f32x4& yi) const {
 #pragma unroll
@@ -191,7 +109,7 @@ __global__ __launch_bounds__(256) void cbn_stats_partial_kernel(const float* __r
 #pragma unroll 2
     for (int64_t r = r0 + rl; r < r1; r += RP) {
       const float* p = x + r * (2 * Cc) + cg * 4;
-      const f32x4 vr = ldq(p), vi = ldq(p + Cc);
+      const f32x4 vr = load4<float>(p), vi = load4<float>(p + Cc);
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const double a = (double)vr[j], b = (double)vi[j];
@@ -203,7 +121,8 @@ __global__ __launch_bounds__(256) void cbn_stats_partial_kernel(const float* __r
       }
     }
   }
-  cbn_block_sum<CBN_NSTAT>(acc, CG, RP, partial + (int64_t)blockIdx.x * Cc * CBN_NSTAT);
+  row_lane_block_sum_2level<CBN_NSTAT>(acc, CG, RP,
+                                       partial + (int64_t)blockIdx.x * Cc * CBN_NSTAT);
 }
 
 // one block per complex channel: moments in fp64, running buffers lerped n_updates times (V before
@@ -215,7 +134,7 @@ __global__ __launch_bounds__(256) void cbn_finalize_kernel(
     float* stats) {
   const int c = blockIdx.x;
   double S[CBN_NSTAT];
-  cbn_channel_sum<CBN_NSTAT>(partial, nblk, Cc, c, S);
+  channel_partial_sum<CBN_NSTAT, 1>(partial, nblk, Cc, c, S);
   if (threadIdx.x != 0) return;
   const double n = (double)rows;
   const double Mr = S[0] / n, Mi = S[1] / n;
@@ -266,7 +185,7 @@ __global__ __launch_bounds__(256) void cbn_apply_kernel(const float* x, float* y
 #pragma unroll 2
   for (int64_t r = r0 + rl; r < r1; r += RP) {
     const int64_t o = r * (2 * Cc) + cg * 4;
-    const f32x4 xr = ldq(x + o), xi = ldq(x + o + Cc);
+    const f32x4 xr = load4<float>(x + o), xi = load4<float>(x + o + Cc);
     f32x4 yr, yi;
     k.y(xr, xi, yr, yi);
     if (alpha) {
@@ -310,13 +229,14 @@ __global__ __launch_bounds__(256) void cbn_bwd_reduce_kernel(
   if (rl < RP) {
     CbnCoef k;
     k.load(coef, Cc, cg * 4);
-    const f32x4 mr = ldq(stats + cg * 4), mi = ldq(stats + Cc + cg * 4);
-    const f32x4 urr = ldq(stats + 5 * Cc + cg * 4), uri = ldq(stats + 6 * Cc + cg * 4),
-                uii = ldq(stats + 7 * Cc + cg * 4);
+    const f32x4 mr = load4<float>(stats + cg * 4), mi = load4<float>(stats + Cc + cg * 4);
+    const f32x4 urr = load4<float>(stats + 5 * Cc + cg * 4);
+    const f32x4 uri = load4<float>(stats + 6 * Cc + cg * 4);
+    const f32x4 uii = load4<float>(stats + 7 * Cc + cg * 4);
     for (int64_t r = r0 + rl; r < r1; r += RP) {
       const int64_t o = r * (2 * Cc) + cg * 4;
-      const f32x4 xr = ldq(x + o), xi = ldq(x + o + Cc);
-      const f32x4 dr = ldq(dy + o), di = ldq(dy + o + Cc);
+      const f32x4 xr = load4<float>(x + o), xi = load4<float>(x + o + Cc);
+      const f32x4 dr = load4<float>(dy + o), di = load4<float>(dy + o + Cc);
       f32x4 yr, yi;
       k.y(xr, xi, yr, yi);
 #pragma unroll
@@ -344,7 +264,8 @@ __global__ __launch_bounds__(256) void cbn_bwd_reduce_kernel(
       }
     }
   }
-  cbn_block_sum<CBN_NBWD>(acc, CG, RP, partial + (int64_t)blockIdx.x * Cc * CBN_NBWD);
+  row_lane_block_sum_2level<CBN_NBWD>(acc, CG, RP,
+                                      partial + (int64_t)blockIdx.x * Cc * CBN_NBWD);
 }
 
 // one block per complex channel; kc [9][Cc]: Arr Ari Air Aii Krr Kri Kii kr ki
@@ -354,7 +275,7 @@ __global__ __launch_bounds__(256) void cbn_bwd_finalize_kernel(
     float* dBr, float* dBi, float* kc, double* alpha_part, int accumulate) {
   const int c = blockIdx.x;
   double S[CBN_NBWD];
-  cbn_channel_sum<CBN_NBWD>(partial, nblk, Cc, c, S);
+  channel_partial_sum<CBN_NBWD, 1>(partial, nblk, Cc, c, S);
   if (threadIdx.x != 0) return;
   const double n = (double)rows;
   const double Mr = stats[c], Mi = stats[Cc + c];
@@ -402,16 +323,6 @@ __global__ __launch_bounds__(256) void cbn_bwd_finalize_kernel(
   if (alpha_part) alpha_part[c] = S[6];
 }
 
-// dalpha (+)= sum over channels of alpha_part (fixed order)
-__global__ void cbn_bwd_alpha_kernel(const double* alpha_part, int Cc, float* dalpha,
-                                     int accumulate) {
-  if (threadIdx.x == 0 && blockIdx.x == 0) {
-    double s = 0;
-    for (int c = 0; c < Cc; ++c) s += alpha_part[c];
-    dalpha[0] = accumulate ? dalpha[0] + (float)s : (float)s;
-  }
-}
-
 __global__ __launch_bounds__(256) void cbn_bwd_apply_kernel(
     const float* __restrict__ x, const float* __restrict__ dy, int64_t rows, int Cc, int64_t rpb,
     const float* __restrict__ coef, const float* __restrict__ alpha, const float* __restrict__ kc,
@@ -429,12 +340,12 @@ __global__ __launch_bounds__(256) void cbn_bwd_apply_kernel(
   k.load(coef, Cc, cg * 4);
   f32x4 A[9];
 #pragma unroll
-  for (int i = 0; i < 9; ++i) A[i] = ldq(kc + i * Cc + cg * 4);
+  for (int i = 0; i < 9; ++i) A[i] = load4<float>(kc + i * Cc + cg * 4);
 #pragma unroll 2
   for (int64_t r = r0 + rl; r < r1; r += RP) {
     const int64_t o = r * (2 * Cc) + cg * 4;
-    const f32x4 xr = ldq(x + o), xi = ldq(x + o + Cc);
-    f32x4 gr = ldq(dy + o), gi = ldq(dy + o + Cc);
+    const f32x4 xr = load4<float>(x + o), xi = load4<float>(x + o + Cc);
+    f32x4 gr = load4<float>(dy + o), gi = load4<float>(dy + o + Cc);
     if (alpha) {
       f32x4 yr, yi;
       k.y(xr, xi, yr, yi);
@@ -451,8 +362,8 @@ __global__ __launch_bounds__(256) void cbn_bwd_apply_kernel(
       oi[j] = fmaf(A[2][j], gr[j], fmaf(A[3][j], gi[j], fmaf(A[5][j], xr[j], fmaf(A[6][j], xi[j], A[8][j]))));
     }
     if (accumulate) {
-      or_ += ldq(dx + o);
-      oi += ldq(dx + o + Cc);
+      or_ += load4<float>(dx + o);
+      oi += load4<float>(dx + o + Cc);
     }
     *reinterpret_cast<f32x4*>(dx + o) = or_;
     *reinterpret_cast<f32x4*>(dx + o + Cc) = oi;
@@ -469,8 +380,6 @@ inline int32_t cbn_pass_blocks(int64_t rows, int32_t C, int64_t cap, int per_thr
 inline bool cbn_shape_ok(int64_t rows, int32_t C) {
   return rows > 0 && C >= 8 && C % 8 == 0 && C <= 2048;
 }
-
-inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 }  // namespace clskd
 
@@ -571,8 +480,7 @@ extern "C" int clskd_cbn_bwd(const float* x, const float* dy, int64_t rows, int3
                      stats, Wrr, Wri, Wii, dWrr, dWri, dWii, dBr, dBi, kc,
                      alpha ? apart : nullptr, accumulate_params);
   if (alpha && dalpha)
-    hipLaunchKernelGGL(cbn_bwd_alpha_kernel, dim3(1), dim3(64), 0, st, apart, Cc, dalpha,
-                       accumulate_params);
+    bn_bwd_alpha(apart, Cc, 1, dalpha, accumulate_params, st);
   if (dx) {
     const int32_t nb = cbn_pass_blocks(rows, C, 4096);
     hipLaunchKernelGGL(cbn_bwd_apply_kernel, dim3(nb), dim3(256), 0, st, x, dy, rows, Cc,

@@ -48,6 +48,10 @@ int knob(KnobId k);
 // finalize (norm.hip): returns the row count the finalize then reads (nblk when not folded).
 // `bit` = 1 backward finalizes, 2 forward (CLSKD_BN_PFOLD mask).
 int fold_partials(double* part, int nblk, int E, int bit, hipStream_t st);
+// The PReLU slope gradient of the BatchNorm and ComplexBatchNorm backwards (norm_bwd.hip):
+// dalpha[h] (+)= sum of alpha_part over the channels of part h of `halves` equal parts, ascending.
+void bn_bwd_alpha(const double* alpha_part, int C, int halves, float* dalpha, int accumulate,
+                  hipStream_t st);
 // CLSKD_OK, or CLSKD_E_ARG (with the error message set) when `value` selects a timing-only mode
 // in a product build.
 int experiment_guard(const char* what, int value);
@@ -95,6 +99,14 @@ inline bool is_lowp(int dt) { return dt == CLSKD_BF16 || dt == CLSKD_F16; }
 inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 
 inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
+
+// blocks of a 256-thread grid-stride pass over n items: at least one, at most `cap`
+inline unsigned grid_for(int64_t n, int64_t cap = 8192) {
+  const int64_t g = cdiv(n, 256);
+  return (unsigned)(g < 1 ? 1 : g > cap ? cap : g);
+}
+
+inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 // compute units of device 0, read once (capi.cpp); 256 when there is no device to ask
 int device_cu_count();

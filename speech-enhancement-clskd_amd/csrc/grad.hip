@@ -314,8 +314,6 @@ __global__ void axpy_f32_kernel(const float* __restrict__ x, float* __restrict__
     y[i] = accumulate ? fmaf(alpha, x[i], y[i]) : alpha * x[i];
 }
 
-inline unsigned grid_for(int64_t n) { return (unsigned)std::min<int64_t>(cdiv(n, 256), 8192); }
-
 // splits of the row axis: about CLSKD_WGRAD_WG workgroups (default 4096), at least 256 rows
 // per split.  The [S][N][K] partials are written once and re-read by wgrad_reduce_kernel, so
 // S trades occupancy against partial traffic.

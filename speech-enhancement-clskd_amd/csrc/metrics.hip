@@ -24,6 +24,7 @@
 #include <math.h>
 
 #include "common.h"
+#include "reduce.h"
 
 namespace clskd {
 
@@ -137,7 +138,6 @@ __device__ double bessel_i0(double x) {
 __global__ __launch_bounds__(1024) void stoi_filter_kernel(int L, int up, int pre_pad, double stop,
                                                            double beta, double* __restrict__ hp) {
   const int M = 2 * L + 1;
-  __shared__ double red[1024];
   const double i0b = bessel_i0(beta);
   double part = 0.0;
   for (int t = threadIdx.x; t < M; t += 1024) {
@@ -149,13 +149,7 @@ __global__ __launch_bounds__(1024) void stoi_filter_kernel(int L, int up, int pr
     hp[pre_pad + t] = h;
     part += h;
   }
-  red[threadIdx.x] = part;
-  __syncthreads();
-  for (int o = 512; o > 0; o >>= 1) {
-    if (threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-    __syncthreads();
-  }
-  const double scale = (double)up / red[0];
+  const double scale = (double)up / block_tree_sum<1024>(part);
   for (int t = threadIdx.x; t < M; t += 1024) hp[pre_pad + t] *= scale;
   for (int t = threadIdx.x; t < pre_pad; t += 1024) hp[t] = 0.0;
 }
@@ -347,14 +341,8 @@ __global__ __launch_bounds__(256) void stoi_corr_kernel(const double* __restrict
     for (int i = 0; i < NSEG; ++i) c += (yp[i] * iy) * ((xs[i] - mxv) * ix);
     acc += c;
   }
-  __shared__ double red[256];
-  red[tid] = acc;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (tid < o) red[tid] += red[tid + o];
-    __syncthreads();
-  }
-  if (tid == 0) d[u] = red[0] / ((double)J * NBAND);
+  acc = block_tree_sum(acc);
+  if (tid == 0) d[u] = acc / ((double)J * NBAND);
 }
 
 // pb_bss SI-SDR per row (float64, no eps): alpha = <r,e>/<r,r>; 10 log10(|a r|^2 / |e - a r|^2)
@@ -365,37 +353,21 @@ __global__ __launch_bounds__(256) void sisdr_rows_f64_kernel(const float* __rest
   const int row = blockIdx.x, tid = threadIdx.x;
   const float* r = ref + row * ldr;
   const float* e = est + row * lde;
-  __shared__ double red[2][256];
-  double re = 0.0, rr = 0.0;
+  double s[2] = {0.0, 0.0};  // <r, e>, <r, r>
   for (int i = tid; i < L; i += 256) {
-    re += (double)r[i] * (double)e[i];
-    rr += (double)r[i] * (double)r[i];
+    s[0] += (double)r[i] * (double)e[i];
+    s[1] += (double)r[i] * (double)r[i];
   }
-  red[0][tid] = re;
-  red[1][tid] = rr;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (tid < o) {
-      red[0][tid] += red[0][tid + o];
-      red[1][tid] += red[1][tid + o];
-    }
-    __syncthreads();
-  }
-  const double energy = red[1][0];
-  const double alpha = red[0][0] / energy;
-  __syncthreads();
+  block_tree_sum<2>(s);
+  const double energy = s[1];
+  const double alpha = s[0] / energy;
   double nn = 0.0;
   for (int i = tid; i < L; i += 256) {
     const double n = (double)e[i] - alpha * (double)r[i];
     nn += n * n;
   }
-  red[0][tid] = nn;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (tid < o) red[0][tid] += red[0][tid + o];
-    __syncthreads();
-  }
-  if (tid == 0) out[row] = 10.0 * log10(alpha * alpha * energy / red[0][0]);
+  nn = block_tree_sum(nn);
+  if (tid == 0) out[row] = 10.0 * log10(alpha * alpha * energy / nn);
 }
 
 }  // namespace clskd

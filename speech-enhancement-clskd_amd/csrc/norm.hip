@@ -1,8 +1,9 @@
 // BatchNorm (train/eval) + PReLU, masking mode 'E', ConviSTFT overlap-add, framing pads,
 // complex-LSTM combine and the ReviewKD ABF attention fusion.  All HBM-bound elementwise /
 // reduction work: float4 (16 B/lane) loads, fp64 accumulation for statistics, deterministic
-// two-level reductions (no float atomics).
+// two-level reductions (block sums of reduce.h, then a finalize; no float atomics).
 #include "common.h"
+#include "reduce.h"
 
 namespace clskd {
 
@@ -32,30 +33,7 @@ __global__ __launch_bounds__(256) void bn_stats_partial_kernel(const T* __restri
       }
     }
   }
-  __shared__ double red[256][9];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    red[tid][j] = s[j];
-    red[tid][4 + j] = q[j];
-  }
-  __syncthreads();
-  if (tid < CG) {
-    double S[4] = {0, 0, 0, 0}, Q[4] = {0, 0, 0, 0};
-    for (int l = 0; l < RP; ++l) {
-      const int t = l * CG + tid;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        S[j] += red[t][j];
-        Q[j] += red[t][4 + j];
-      }
-    }
-    double* p = partial + ((int64_t)blockIdx.x * C + tid * 4) * 2;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      p[2 * j] = S[j];
-      p[2 * j + 1] = Q[j];
-    }
-  }
+  row_lane_block_sum<2>(C, partial, s, q);
 }
 
 // one block per channel: sum partials in a fixed order (16-B {sum, sumsq} loads, eight in flight
@@ -408,13 +386,6 @@ __global__ void zero_f64_kernel(double* p, int64_t n) {
     p[i] = 0.0;
 }
 
-inline unsigned grid_for(int64_t n, int block = 256, int64_t cap = 8192) {
-  int64_t g = cdiv(n, block);
-  if (g < 1) g = 1;
-  if (g > cap) g = cap;
-  return (unsigned)g;
-}
-
 
 // Frame-major spectrum -> BFTC encoder input: out[b][f][t][0|1] = spec[b][t][re0|im0 + f].
 // 64 frames x 32 bins per block through LDS: reads are 128-B bin runs of a frame, writes are
@@ -529,7 +500,7 @@ extern "C" int clskd_bn_stats_partial(const void* x, int64_t rows, int32_t C, do
   CLSKD_CHECK_ARG(x && partial, "bn_stats: null pointer");
   CLSKD_CHECK_SHAPE(rows > 0 && C >= 4 && C % 4 == 0 && C <= 1024, "bn_stats: bad C=%d", C);
   CLSKD_CHECK_SHAPE(nblk >= 1, "bn_stats: nblk");
-  CLSKD_CHECK_ARG(((uintptr_t)x & 15) == 0, "bn_stats: x must be 16-byte aligned");
+  CLSKD_CHECK_ARG(aligned16(x), "bn_stats: x must be 16-byte aligned");
   CLSKD_CHECK_ARG(dtype == CLSKD_F32 || dtype == CLSKD_BF16 || dtype == CLSKD_F16, "bn_stats: dtype");
   const int64_t rpb = cdiv(rows, nblk);
   if (dtype == CLSKD_BF16)
@@ -549,7 +520,7 @@ extern "C" int clskd_bn_compact(const double* partial, int32_t nblk, int32_t C, 
                                 double* out, void* stream) {
   CLSKD_CHECK_ARG(partial && out, "bn_compact: null pointer");
   CLSKD_CHECK_SHAPE(nblk > 0 && C > 0 && group >= 4, "bn_compact: shape");
-  CLSKD_CHECK_ARG(((uintptr_t)partial & 15) == 0 && ((uintptr_t)out & 15) == 0,
+  CLSKD_CHECK_ARG(aligned16(partial) && aligned16(out),
                   "bn_compact: partials must be 16-byte aligned");
   hipLaunchKernelGGL(bn_compact_kernel, dim3((unsigned)cdiv(nblk, group), (unsigned)cdiv(C, 64)),
                      dim3(256), 0, as_stream(stream), partial, nblk, C, group, out);
@@ -564,7 +535,7 @@ extern "C" int clskd_bn_finalize(double* partial, int32_t nblk, int64_t rows, in
                                  float* var_out, void* stream) {
   CLSKD_CHECK_ARG(partial && scale && shift, "bn_finalize: null pointer");
   CLSKD_CHECK_SHAPE(C > 0 && nblk > 0 && rows > 0, "bn_finalize: shape");
-  CLSKD_CHECK_ARG(((uintptr_t)partial & 15) == 0, "bn_finalize: partials must be 16-byte aligned");
+  CLSKD_CHECK_ARG(aligned16(partial), "bn_finalize: partials must be 16-byte aligned");
   if (skip_kernel(SKIP_BN_FINALIZE)) return CLSKD_OK;
   nblk = fold_partials(partial, nblk, 2 * C, 2, as_stream(stream));
   hipLaunchKernelGGL(bn_finalize_kernel, dim3(C), dim3(BNF_T), 0, as_stream(stream), partial, nblk,
@@ -590,7 +561,7 @@ static int bn_apply_impl(const void* x, void* y, int64_t rows, int32_t C, const 
                          void* stream) {
   CLSKD_CHECK_ARG(x && y && scale && shift, "bn_apply: null pointer");
   CLSKD_CHECK_SHAPE(C % 8 == 0 && rows > 0, "bn_apply: C=%d must be a multiple of 8", C);
-  CLSKD_CHECK_ARG(((uintptr_t)x & 15) == 0 && ((uintptr_t)y & 15) == 0, "bn_apply: alignment");
+  CLSKD_CHECK_ARG(aligned16(x) && aligned16(y), "bn_apply: alignment");
   CLSKD_CHECK_ARG(dtype == CLSKD_F32 || dtype == CLSKD_BF16 || dtype == CLSKD_F16, "bn_apply: dtype");
   if (skip_kernel(SKIP_BN_APPLY)) return CLSKD_OK;
   const int64_t items = rows * C / 8;

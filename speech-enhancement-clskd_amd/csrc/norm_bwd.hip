@@ -1,28 +1,16 @@
 // Backward of the elementwise / normalisation ops of the CLSKD step (student side):
 // BatchNorm2d(train) + PReLU, ReviewKD ABF attention fusion and nearest upsampling, masking
 // mode 'E', ConviSTFT overlap-add + clamp, framing pads, the STFT log-magnitude L1 loss and the
-// complex-LSTM output combine.  HBM-bound passes; statistics reductions in fp64 with fixed
-// orders (no float atomics), so every gradient is bitwise repeatable.
+// complex-LSTM output combine; the BatchNorm backward also serves asteroid's OnReIm pair
+// (clskd_bn_bwd_reim: a slope per channel half).  HBM-bound passes; statistics reductions in fp64
+// with fixed orders (reduce.h; no float atomics), so every gradient is bitwise repeatable.
 #include <algorithm>
 #include <type_traits>
 
 #include "common.h"
+#include "reduce.h"
 
 namespace clskd {
-
-typedef __bf16 bf16x4b __attribute__((ext_vector_type(4)));
-
-template <typename T>
-__device__ __forceinline__ f32x4 ld4(const T* p);
-template <>
-__device__ __forceinline__ f32x4 ld4<float>(const float* p) {
-  return *reinterpret_cast<const f32x4*>(p);
-}
-template <>
-__device__ __forceinline__ f32x4 ld4<__bf16>(const __bf16* p) {
-  const bf16x4b v = *reinterpret_cast<const bf16x4b*>(p);
-  return f32x4{(float)v[0], (float)v[1], (float)v[2], (float)v[3]};
-}
 
 // 4 channels as their raw storage vector (loaded without conversion) and its fp32 widening
 template <typename T> struct Raw4;
@@ -32,7 +20,7 @@ template <> struct Raw4<float> {
   static __device__ __forceinline__ f32x4 cvt(V v) { return v; }
 };
 template <> struct Raw4<__bf16> {
-  typedef bf16x4b V;
+  typedef bf16x4 V;
   static __device__ __forceinline__ V ld(const __bf16* p) { return *reinterpret_cast<const V*>(p); }
   static __device__ __forceinline__ f32x4 cvt(V v) {
     return f32x4{(float)v[0], (float)v[1], (float)v[2], (float)v[3]};
@@ -46,8 +34,11 @@ template <> struct Raw4<__bf16> {
 //   dbeta = sum dz, dgamma = sum dz*xhat, dalpha = sum_{y_bn<=0} y_bn*dy
 //   dx = k1*dz + k2*x + k3   with k1 = gamma*rstd, k2 = -gamma*rstd^2*dgamma/n,
 //                              k3 = -gamma*rstd*dbeta/n + gamma*rstd^2*mean*dgamma/n
+// REIM (asteroid's OnReIm(BatchNorm2d) + OnReIm(PReLU), clskd_bn_bwd_reim): alpha is required and
+// holds two slopes, alpha[0] for the channels [0, C/2) and alpha[1] for [C/2, C), and dalpha one
+// sum per half; everything else is the same pass.
 // ------------------------------------------------------------------------------------------
-template <typename T>
+template <typename T, bool REIM = false>
 __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(
     const T* __restrict__ x, const float* __restrict__ dy, int64_t rows, int C, int64_t rpb,
     const float* __restrict__ scale, const float* __restrict__ shift,
@@ -60,8 +51,9 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(
   const int rl = tid / CG;
   const int64_t r0 = (int64_t)blockIdx.x * rpb;
   const int64_t r1 = min(rows, r0 + rpb);
-  const float al = alpha ? alpha[0] : 1.f;
-  f32x4 sc, sh, mu, rs;
+  const bool prelu = REIM || alpha;
+  const float a0 = prelu ? alpha[0] : 1.f;
+  f32x4 sc, sh, mu, rs, al;
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
     const int c = (cg * 4 + j) % C;
@@ -69,20 +61,21 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(
     sh[j] = shift[c];
     mu[j] = mean[c];
     rs[j] = (float)(1.0 / sqrt((double)var[c] + (double)eps));
+    al[j] = REIM && 2 * c >= C ? alpha[1] : a0;
   }
   double sb[4] = {0, 0, 0, 0}, sg[4] = {0, 0, 0, 0}, sa[4] = {0, 0, 0, 0};
   if (rl < RP) {
     for (int64_t r = r0 + rl; r < r1; r += RP) {
-      const f32x4 xv = ld4<T>(x + r * C + cg * 4);
+      const f32x4 xv = load4<T>(x + r * C + cg * 4);
       const f32x4 gv = *reinterpret_cast<const f32x4*>(dy + r * C + cg * 4);
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const float yb = fmaf(xv[j], sc[j], sh[j]);
         float dz = gv[j];
-        if (alpha) {
+        if (prelu) {
           if (!(yb > 0.f)) {
             sa[j] += (double)yb * (double)gv[j];
-            dz = al * gv[j];
+            dz = al[j] * gv[j];
           }
         }
         const float xh = (xv[j] - mu[j]) * rs[j];
@@ -91,81 +84,21 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(
       }
     }
   }
-  __shared__ double red[256][13];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    red[tid][j] = sb[j];
-    red[tid][4 + j] = sg[j];
-    red[tid][8 + j] = sa[j];
-  }
-  __syncthreads();
-  if (tid < CG) {
-    double B[4] = {0, 0, 0, 0}, G[4] = {0, 0, 0, 0}, A[4] = {0, 0, 0, 0};
-    for (int l = 0; l < RP; ++l) {
-      const int t = l * CG + tid;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        B[j] += red[t][j];
-        G[j] += red[t][4 + j];
-        A[j] += red[t][8 + j];
-      }
-    }
-    double* p = partial + ((int64_t)blockIdx.x * C + tid * 4) * 3;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      p[3 * j] = B[j];
-      p[3 * j + 1] = G[j];
-      p[3 * j + 2] = A[j];
-    }
-  }
+  row_lane_block_sum<3>(C, partial, sb, sg, sa);
 }
 
-// one block per channel; writes dgamma/dbeta (accumulate optional), k[3][C], alpha_part[C]
+// one block per channel; writes dgamma/dbeta (accumulate optional), k[3][C], alpha_part[C].
+// Eight independent accumulators: eight strided partial rows in flight per thread (one L2 round
+// trip per 256 rows was latency-bound at nblk ~ 16k).
 __global__ __launch_bounds__(256) void bn_bwd_finalize_kernel(
     const double* __restrict__ partial, int nblk, int64_t rows, int C, const float* gamma,
     const float* mean, const float* var, float eps, float* dgamma, float* dbeta, float* k,
     double* alpha_part, int accumulate) {
   const int c = blockIdx.x;
-  const int tid = threadIdx.x;
-  // eight independent accumulators: eight strided partial rows in flight per thread (the loop
-  // was one L2 round trip per 256 rows — latency-bound at nblk ~ 16k); fixed combine order
-  double sb[8] = {0, 0, 0, 0, 0, 0, 0, 0}, sg[8] = {0, 0, 0, 0, 0, 0, 0, 0},
-         sa[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  int b = tid;
-  for (; b + 7 * 256 < nblk; b += 8 * 256) {
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-      const double* p = partial + ((int64_t)(b + u * 256) * C + c) * 3;
-      sb[u] += p[0];
-      sg[u] += p[1];
-      sa[u] += p[2];
-    }
-  }
-  for (; b < nblk; b += 256) {
-    const double* p = partial + ((int64_t)b * C + c) * 3;
-    sb[0] += p[0];
-    sg[0] += p[1];
-    sa[0] += p[2];
-  }
-  double SB = ((sb[0] + sb[1]) + (sb[2] + sb[3])) + ((sb[4] + sb[5]) + (sb[6] + sb[7]));
-  double SG = ((sg[0] + sg[1]) + (sg[2] + sg[3])) + ((sg[4] + sg[5]) + (sg[6] + sg[7]));
-  const double SA = ((sa[0] + sa[1]) + (sa[2] + sa[3])) + ((sa[4] + sa[5]) + (sa[6] + sa[7]));
-  __shared__ double r0[256], r1[256], r2[256];
-  r0[tid] = SB;
-  r1[tid] = SG;
-  r2[tid] = SA;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (tid < o) {
-      r0[tid] += r0[tid + o];
-      r1[tid] += r1[tid + o];
-      r2[tid] += r2[tid + o];
-    }
-    __syncthreads();
-  }
-  if (tid == 0) {
-    SB = r0[0];
-    SG = r1[0];
+  double S[3];  // dbeta, dgamma, dalpha sums
+  channel_partial_sum<3, 8>(partial, nblk, C, c, S);
+  if (threadIdx.x == 0) {
+    const double SB = S[0], SG = S[1];
     const double n = (double)rows;
     const double rs = 1.0 / sqrt((double)var[c] + (double)eps);
     const double g = gamma ? (double)gamma[c] : 1.0;
@@ -174,27 +107,45 @@ __global__ __launch_bounds__(256) void bn_bwd_finalize_kernel(
     k[2 * C + c] = (float)(-g * rs * SB / n + g * rs * rs * (double)mean[c] * SG / n);
     if (dgamma) dgamma[c] = accumulate ? dgamma[c] + (float)SG : (float)SG;
     if (dbeta) dbeta[c] = accumulate ? dbeta[c] + (float)SB : (float)SB;
-    if (alpha_part) alpha_part[c] = r2[0];
+    if (alpha_part) alpha_part[c] = S[2];
   }
 }
 
-// dalpha (+)= sum over channels of alpha_part (fixed order)
+// dalpha[h] (+)= sum of alpha_part over the channels of part h of HALVES equal parts, ascending
+// (1: every channel, one slope; 2: one sum per half), one thread per part, one block.  HALVES is
+// a template argument so that the one-slope form keeps uniform addresses (scalar loads): with a
+// run-time count its partials came by vector loads, 0.8 us more per clskd_bn_bwd call.
+template <int HALVES>
 __global__ void bn_bwd_alpha_kernel(const double* alpha_part, int C, float* dalpha, int accumulate) {
-  if (threadIdx.x == 0 && blockIdx.x == 0) {
+  const int h = HALVES == 1 ? 0 : threadIdx.x;
+  if (blockIdx.x == 0 && threadIdx.x < HALVES) {
+    const int n = C / HALVES;
     double s = 0;
-    for (int c = 0; c < C; ++c) s += alpha_part[c];
-    dalpha[0] = accumulate ? dalpha[0] + (float)s : (float)s;
+    for (int c = h * n; c < (h + 1) * n; ++c) s += alpha_part[c];
+    dalpha[h] = accumulate ? dalpha[h] + (float)s : (float)s;
   }
 }
 
-template <typename T, typename GT = float>
+void bn_bwd_alpha(const double* alpha_part, int C, int halves, float* dalpha, int accumulate,
+                  hipStream_t st) {
+  if (halves == 2)
+    hipLaunchKernelGGL(bn_bwd_alpha_kernel<2>, dim3(1), dim3(64), 0, st, alpha_part, C, dalpha,
+                       accumulate);
+  else
+    hipLaunchKernelGGL(bn_bwd_alpha_kernel<1>, dim3(1), dim3(64), 0, st, alpha_part, C, dalpha,
+                       accumulate);
+}
+
+template <typename T, typename GT = float, bool REIM = false>
 __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(
     const T* __restrict__ x, const GT* __restrict__ dy, int64_t rows, int C,
     const float* __restrict__ scale, const float* __restrict__ shift,
     const float* __restrict__ alpha, const float* __restrict__ k, float* __restrict__ dx,
     int accumulate) {
   const int64_t nq = rows * C / 4;
-  const float al = alpha ? alpha[0] : 1.f;
+  const bool prelu = REIM || alpha;
+  const float a0 = prelu ? alpha[0] : 1.f;
+  const float a1 = REIM ? alpha[1] : a0;
   // channel of the thread's first quad, then advanced by the grid stride (mod C): no 64-bit
   // modulo per quad; the per-channel vectors are 16-B loads (C % 4 == 0, 16-B aligned: host)
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
@@ -202,18 +153,20 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(
   const int cstep = (int)((stride * 4) % C);
   int c0 = (int)((q0 * 4) % C);
   for (int64_t q = q0; q < nq; q += stride) {
-    const f32x4 xv = ld4<T>(x + q * 4);
+    const f32x4 xv = load4<T>(x + q * 4);
     const f32x4 gv = load4<GT>(dy + q * 4);
     const f32x4 k0 = *reinterpret_cast<const f32x4*>(k + c0);
     const f32x4 k1 = *reinterpret_cast<const f32x4*>(k + C + c0);
     const f32x4 k2 = *reinterpret_cast<const f32x4*>(k + 2 * C + c0);
     f32x4 dz = gv;
-    if (alpha) {
+    if (prelu) {
       const f32x4 sc = *reinterpret_cast<const f32x4*>(scale + c0);
       const f32x4 sh = *reinterpret_cast<const f32x4*>(shift + c0);
 #pragma unroll
-      for (int j = 0; j < 4; ++j)
+      for (int j = 0; j < 4; ++j) {
+        const float al = REIM && 2 * (c0 + j) >= C ? a1 : a0;
         if (!(fmaf(xv[j], sc[j], sh[j]) > 0.f)) dz[j] = al * gv[j];
+      }
     }
     f32x4 o;
 #pragma unroll
@@ -232,21 +185,13 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(
 // a_k = (sum_c dout_c * {x,y}_c) * z_k (1 - z_k).  dx is w.r.t. the BN1 output x; dy is w.r.t.
 // the UPSAMPLED residual (reduce with clskd_nearest_down_sum).
 // ------------------------------------------------------------------------------------------
-__device__ __forceinline__ int nearest_src_b(int dst, int in_size, int out_size) {
-  if (out_size == in_size) return dst;
-  if (out_size == 2 * in_size) return dst >> 1;
-  const float scale = (float)in_size / (float)out_size;
-  const int s = (int)floorf((float)dst * scale);
-  return s < in_size - 1 ? s : in_size - 1;
-}
-
-// smallest dst with nearest_src(dst) >= s (nearest_src is non-decreasing in dst)
-__device__ __forceinline__ int first_dst_b(int s, int in_size, int out_size) {
-  if (out_size == in_size) return s;           // the nearest_src_b fast paths, inverted
+// smallest dst with nearest_src(dst) >= s (nearest_src, common.h, is non-decreasing in dst)
+__device__ __forceinline__ int first_dst(int s, int in_size, int out_size) {
+  if (out_size == in_size) return s;           // the nearest_src fast paths, inverted
   if (out_size == 2 * in_size) return 2 * s;
   int d0 = (int)((double)s * out_size / in_size) - 2;
   if (d0 < 0) d0 = 0;
-  while (d0 < out_size && nearest_src_b(d0, in_size, out_size) < s) ++d0;
+  while (d0 < out_size && nearest_src(d0, in_size, out_size) < s) ++d0;
   return d0;
 }
 
@@ -294,7 +239,7 @@ __global__ __launch_bounds__(256) void abf_fuse_bwd_kernel(
     w1y[j] = w[192 + c + j];
   }
   const float b0 = bias[0], b1 = bias[1];
-  // next grid an exact 1x / 2x upsampling in each axis (nearest_src_b's fast paths): the children
+  // next grid an exact 1x / 2x upsampling in each axis (nearest_src's fast paths): the children
   // of (f, t) are {rf*f, rf*f + 1} x {rt*t, rt*t + 1}, no search loop (rf = 0: general grids)
   int rf = 0, rt = 0;
   if (dnext && (F2 == F || F2 == 2 * F) && (T2 == T || T2 == 2 * T)) {
@@ -316,8 +261,8 @@ __global__ __launch_bounds__(256) void abf_fuse_bwd_kernel(
     o.t = (int)(p32 - bf * (uint32_t)T);
     o.b = (int)(bf / (uint32_t)F);
     o.f = (int)(bf - (uint32_t)o.b * (uint32_t)F);
-    const int fr = nearest_src_b(o.f, Fr, F);
-    const int tr = nearest_src_b(o.t, Tr, T);
+    const int fr = nearest_src(o.f, Fr, F);
+    const int tr = nearest_src(o.t, Tr, T);
     const GT* gp = dout + p * 64 + c;
     const GT* q = gp;  // children of a 1x / 2x next grid (rf = 0: dout again, unused)
     int64_t df = 0, dt = 0;
@@ -349,9 +294,9 @@ __global__ __launch_bounds__(256) void abf_fuse_bwd_kernel(
         if (rt == 2) g += Raw4<GT>::cvt(o.c11);
       }
     } else if (dnext) {  // children of (f, t) on the next level's grid
-      const int fa = first_dst_b(o.f, F, F2), ta = first_dst_b(o.t, T, T2);
-      for (int f2 = fa; f2 < F2 && nearest_src_b(f2, F, F2) == o.f; ++f2)
-        for (int t2 = ta; t2 < T2 && nearest_src_b(t2, T, T2) == o.t; ++t2)
+      const int fa = first_dst(o.f, F, F2), ta = first_dst(o.t, T, T2);
+      for (int f2 = fa; f2 < F2 && nearest_src(f2, F, F2) == o.f; ++f2)
+        for (int t2 = ta; t2 < T2 && nearest_src(t2, T, T2) == o.t; ++t2)
           g += load4<GT>(dnext + ((((int64_t)o.b * F2 + f2) * T2 + t2) * 64) + c);
     }
     float d0 = 0.f, d1 = 0.f, e0 = 0.f, e1 = 0.f;
@@ -434,14 +379,6 @@ __global__ __launch_bounds__(256) void abf_fuse_bwd_kernel(
 }
 
 // out[b][fr][tr][c] (+)= sum of g[b][f][t][c] over the (f, t) whose nearest source is (fr, tr)
-__device__ __forceinline__ int first_dst(int s, int in_size, int out_size) {
-  // smallest dst with nearest_src(dst) >= s (nearest_src is non-decreasing in dst)
-  int d0 = (int)((double)s * out_size / in_size) - 2;
-  if (d0 < 0) d0 = 0;
-  while (d0 < out_size && nearest_src_b(d0, in_size, out_size) < s) ++d0;
-  return d0;
-}
-
 template <typename GT>
 __global__ __launch_bounds__(256) void nearest_down_sum_kernel(
     const GT* __restrict__ g, int B, int F, int T, int Fr, int Tr, int C,
@@ -458,8 +395,8 @@ __global__ __launch_bounds__(256) void nearest_down_sum_kernel(
     const int b = (int)(bf / Fr);
     const int fa = first_dst(fr, Fr, F), ta = first_dst(tr, Tr, T);
     f32x4 s = {0.f, 0.f, 0.f, 0.f};
-    for (int f = fa; f < F && nearest_src_b(f, Fr, F) == fr; ++f)
-      for (int t = ta; t < T && nearest_src_b(t, Tr, T) == tr; ++t)
+    for (int f = fa; f < F && nearest_src(f, Fr, F) == fr; ++f)
+      for (int t = ta; t < T && nearest_src(t, Tr, T) == tr; ++t)
         s += load4<GT>(g + ((((int64_t)b * F + f) * T + t) * C) + cq * 4);
     float* op = out + pix * C + cq * 4;
     if (accumulate) s += *reinterpret_cast<const f32x4*>(op);
@@ -730,7 +667,7 @@ __global__ __launch_bounds__(256) void spkd_bn_bwd_reduce_kernel(
 #pragma unroll 1
       for (int b = 0; b < B; ++b) {
         const f32x4 x = parks<T, BM>() ? Raw4<T>::cvt(park[b * 256 + tid])
-                                         : ld4<T>(base + b * sB);
+                                         : load4<T>(base + b * sB);
         f32x4 dz = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int k = 0; k < BM; ++k)
@@ -748,31 +685,8 @@ __global__ __launch_bounds__(256) void spkd_bn_bwd_reduce_kernel(
       }
     }
   }
-  __shared__ double red[256][9];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    red[tid][j] = sb[j];
-    red[tid][4 + j] = sg[j];
-  }
-  __syncthreads();
-  if (tid < CG) {
-    double Bv[4] = {0, 0, 0, 0}, G[4] = {0, 0, 0, 0};
-    for (int l = 0; l < RP; ++l) {
-      const int t = l * CG + tid;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        Bv[j] += red[t][j];
-        G[j] += red[t][4 + j];
-      }
-    }
-    double* q = partial + ((int64_t)blockIdx.x * C + tid * 4) * 3;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      q[3 * j] = Bv[j];
-      q[3 * j + 1] = G[j];
-      q[3 * j + 2] = 0.0;
-    }
-  }
+  // bn_bwd_finalize_kernel's rows of 3: the PReLU term is written as 0.0
+  row_lane_block_sum<3>(C, partial, sb, sg);
 }
 
 template <typename T, typename OT, int BM, bool EX = false>
@@ -803,7 +717,7 @@ __global__ __launch_bounds__(256) void spkd_bn_bwd_apply_kernel(
 #pragma unroll 1
     for (int b = 0; b < B; ++b) {
       const f32x4 x = parks<T, BM>() ? Raw4<T>::cvt(park[b * 256 + threadIdx.x])
-                                       : ld4<T>(base + b * sB);
+                                       : load4<T>(base + b * sB);
       f32x4 dz = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int kk = 0; kk < BM; ++kk)
@@ -813,10 +727,10 @@ __global__ __launch_bounds__(256) void spkd_bn_bwd_apply_kernel(
       for (int j = 0; j < 4; ++j) o[j] = fmaf(k1[j], dz[j], fmaf(k2[j], x[j], k3[j]));
       OT* dst = draw + b * sB + p * C + c0;
       if constexpr (sizeof(OT) == 2) {
-        bf16x4b ob;
+        bf16x4 ob;
 #pragma unroll
         for (int j = 0; j < 4; ++j) ob[j] = (__bf16)o[j];
-        *reinterpret_cast<bf16x4b*>(dst) = ob;
+        *reinterpret_cast<bf16x4*>(dst) = ob;
       } else {
         *reinterpret_cast<f32x4*>(dst) = o;
       }
@@ -923,10 +837,6 @@ __global__ __launch_bounds__(256) void bn_bwd_conv1x1_kernel(
   }
 }
 
-inline unsigned grid_of(int64_t n, int64_t cap = 8192) {
-  return (unsigned)std::max<int64_t>(1, std::min<int64_t>(cdiv(n, 256), cap));
-}
-
 }  // namespace clskd
 
 using namespace clskd;
@@ -934,6 +844,34 @@ using namespace clskd;
 extern "C" int32_t clskd_bn_bwd_blocks(int64_t rows, int32_t C) {
   (void)C;
   return (int32_t)std::max<int64_t>(1, std::min<int64_t>(1024, cdiv(rows, 512)));
+}
+
+// The launches of clskd_bn_bwd and clskd_bn_bwd_reim (arguments validated by the entry): reduce,
+// finalize, dalpha when wanted, and the apply unless dx is NULL (coefficients only: k at
+// work + nblk*C*3 doubles, the apply then runs in a consumer).
+template <typename T, bool REIM>
+static int bn_bwd_launch(const char* name, const T* x, const float* dy, int64_t rows, int32_t C,
+                         const float* scale, const float* shift, const float* mean,
+                         const float* var, float eps, const float* gamma, const float* alpha,
+                         double* work, int32_t nblk, float* dgamma, float* dbeta, float* dalpha,
+                         float* dx, int32_t accumulate_dx, int32_t accumulate_params,
+                         hipStream_t st) {
+  // work layout: partial[nblk][C][3] | k[3C] (as floats) | alpha_part[C]
+  double* partial = work;
+  float* k = reinterpret_cast<float*>(work + (int64_t)nblk * C * 3);
+  double* apart = work + (int64_t)nblk * C * 3 + cdiv(3 * C, 2);
+  hipLaunchKernelGGL((bn_bwd_reduce_kernel<T, REIM>), dim3(nblk), dim3(256), 0, st, x, dy, rows, C,
+                     cdiv(rows, nblk), scale, shift, mean, var, eps, alpha, partial);
+  hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(C), dim3(256), 0, st, partial, nblk, rows, C,
+                     gamma, mean, var, eps, dgamma, dbeta, k, alpha ? apart : nullptr,
+                     accumulate_params);
+  if (alpha && dalpha)
+    bn_bwd_alpha(apart, C, REIM ? 2 : 1, dalpha, accumulate_params, st);
+  if (dx)
+    hipLaunchKernelGGL((bn_bwd_apply_kernel<T, float, REIM>), dim3(grid_for(rows * C / 4)),
+                       dim3(256), 0, st, x, dy, rows, C, scale, shift, alpha, k, dx, accumulate_dx);
+  CLSKD_LAUNCH_CHECK(name);
+  return CLSKD_OK;
 }
 
 extern "C" int clskd_bn_bwd(const void* x, const float* dy, int64_t rows, int32_t C,
@@ -946,40 +884,34 @@ extern "C" int clskd_bn_bwd(const void* x, const float* dy, int64_t rows, int32_
   CLSKD_CHECK_SHAPE(rows > 0 && C >= 4 && C % 4 == 0 && C <= 1024 && nblk >= 1,
                     "bn_bwd: rows=%lld C=%d nblk=%d", (long long)rows, C, nblk);
   CLSKD_CHECK_ARG(dtype == CLSKD_F32 || dtype == CLSKD_BF16, "bn_bwd: dtype");
-  CLSKD_CHECK_ARG(((uintptr_t)work & 15) == 0 &&
-                      (!alpha || (((uintptr_t)scale & 15) == 0 && ((uintptr_t)shift & 15) == 0)),
+  CLSKD_CHECK_ARG(aligned16(work) && (!alpha || (aligned16(scale) && aligned16(shift))),
                   "bn_bwd: work (and scale/shift with PReLU) must be 16-byte aligned");
-  hipStream_t st = as_stream(stream);
-  // work layout: partial[nblk][C][3] | k[3C] (as floats) | alpha_part[C]
-  double* partial = work;
-  float* k = reinterpret_cast<float*>(work + (int64_t)nblk * C * 3);
-  double* apart = work + (int64_t)nblk * C * 3 + cdiv(3 * C, 2);
-  const int64_t rpb = cdiv(rows, nblk);
   if (dtype == CLSKD_BF16)
-    hipLaunchKernelGGL(bn_bwd_reduce_kernel<__bf16>, dim3(nblk), dim3(256), 0, st,
-                       (const __bf16*)x, dy, rows, C, rpb, scale, shift, mean, var, eps, alpha, partial);
-  else
-    hipLaunchKernelGGL(bn_bwd_reduce_kernel<float>, dim3(nblk), dim3(256), 0, st, (const float*)x,
-                       dy, rows, C, rpb, scale, shift, mean, var, eps, alpha, partial);
-  hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(C), dim3(256), 0, st, partial, nblk, rows, C,
-                     gamma, mean, var, eps, dgamma, dbeta, k, alpha ? apart : nullptr,
-                     accumulate_params);
-  if (alpha && dalpha)
-    hipLaunchKernelGGL(bn_bwd_alpha_kernel, dim3(1), dim3(64), 0, st, apart, C, dalpha,
-                       accumulate_params);
-  if (!dx) {  // coefficients only (k at work + nblk*C*3 doubles): the apply runs in a consumer
-    CLSKD_LAUNCH_CHECK("bn_bwd");
-    return CLSKD_OK;
-  }
-  const int64_t nq = rows * C / 4;
-  if (dtype == CLSKD_BF16)
-    hipLaunchKernelGGL(bn_bwd_apply_kernel<__bf16>, dim3(grid_of(nq)), dim3(256), 0, st,
-                       (const __bf16*)x, dy, rows, C, scale, shift, alpha, k, dx, accumulate_dx);
-  else
-    hipLaunchKernelGGL(bn_bwd_apply_kernel<float>, dim3(grid_of(nq)), dim3(256), 0, st,
-                       (const float*)x, dy, rows, C, scale, shift, alpha, k, dx, accumulate_dx);
-  CLSKD_LAUNCH_CHECK("bn_bwd");
-  return CLSKD_OK;
+    return bn_bwd_launch<__bf16, false>("bn_bwd", (const __bf16*)x, dy, rows, C, scale, shift, mean,
+                                        var, eps, gamma, alpha, work, nblk, dgamma, dbeta, dalpha,
+                                        dx, accumulate_dx, accumulate_params, as_stream(stream));
+  return bn_bwd_launch<float, false>("bn_bwd", (const float*)x, dy, rows, C, scale, shift, mean,
+                                     var, eps, gamma, alpha, work, nblk, dgamma, dbeta, dalpha, dx,
+                                     accumulate_dx, accumulate_params, as_stream(stream));
+}
+
+extern "C" int clskd_bn_bwd_reim(const float* x, const float* dy, int64_t rows, int32_t C,
+                                 const float* scale, const float* shift, const float* mean,
+                                 const float* var, float eps, const float* gamma,
+                                 const float* alpha_re_im, double* work, int32_t nblk,
+                                 float* dgamma, float* dbeta, float* dalpha_re_im, float* dx,
+                                 int32_t accumulate_dx, int32_t accumulate_params, void* stream) {
+  CLSKD_CHECK_ARG(x && dy && scale && shift && mean && var && alpha_re_im && work && dx,
+                  "bn_bwd_reim: null pointer");
+  CLSKD_CHECK_SHAPE(rows > 0 && C >= 4 && C % 4 == 0 && C <= 1024 && nblk >= 1,
+                    "bn_bwd_reim: rows=%lld C=%d nblk=%d (C: a multiple of 4, two equal halves)",
+                    (long long)rows, C, nblk);
+  CLSKD_CHECK_ARG(aligned16(work) && aligned16(scale) && aligned16(shift) && aligned16(x) &&
+                      aligned16(dy) && aligned16(dx),
+                  "bn_bwd_reim: x, dy, dx, scale, shift and work must be 16-byte aligned");
+  return bn_bwd_launch<float, true>("bn_bwd_reim", x, dy, rows, C, scale, shift, mean, var, eps,
+                                    gamma, alpha_re_im, work, nblk, dgamma, dbeta, dalpha_re_im, dx,
+                                    accumulate_dx, accumulate_params, as_stream(stream));
 }
 
 extern "C" int64_t clskd_bn_bwd_workspace(int32_t nblk, int32_t C) {
@@ -1038,8 +970,7 @@ extern "C" int clskd_bn_bwd_conv1x1(const void* x, int32_t dtype, const void* dy
   CLSKD_CHECK_ARG((dtype == CLSKD_F32 || dtype == CLSKD_BF16) &&
                       (dy_dtype == CLSKD_F32 || dy_dtype == CLSKD_BF16),
                   "bn_bwd_conv1x1: dtype");
-  CLSKD_CHECK_ARG(((uintptr_t)x & 15) == 0 && ((uintptr_t)dy & 15) == 0 &&
-                      ((uintptr_t)out & 15) == 0 && ((uintptr_t)k & 15) == 0,
+  CLSKD_CHECK_ARG(aligned16(x) && aligned16(dy) && aligned16(out) && aligned16(k),
                   "bn_bwd_conv1x1: x, dy, k, out must be 16-byte aligned");
   hipStream_t st = as_stream(stream);
   const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(cdiv(rows, 32), 8192));
@@ -1080,7 +1011,7 @@ extern "C" int clskd_bn_bwd_from_partials(const void* x, const void* dy, int64_t
   CLSKD_CHECK_ARG(dy_dtype == CLSKD_F32 || dy_dtype == CLSKD_BF16,
                   "bn_bwd_from_partials: dy_dtype must be CLSKD_F32 or CLSKD_BF16");
   CLSKD_CHECK_SHAPE(rows > 0 && C >= 4 && C % 4 == 0 && nblk >= 1, "bn_bwd_from_partials: shape");
-  CLSKD_CHECK_ARG(((uintptr_t)kbuf & 15) == 0, "bn_bwd_from_partials: kbuf must be 16-byte aligned");
+  CLSKD_CHECK_ARG(aligned16(kbuf), "bn_bwd_from_partials: kbuf must be 16-byte aligned");
   hipStream_t st = as_stream(stream);
   nblk = fold_partials(partial, nblk, 3 * C, 1, st);
   hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(C), dim3(256), 0, st, partial, nblk, rows, C,
@@ -1091,7 +1022,7 @@ extern "C" int clskd_bn_bwd_from_partials(const void* x, const void* dy, int64_t
   }
   const int64_t nq = rows * C / 4;
 #define BN_APPLY_LAUNCH(T, GT)                                                                  \
-  hipLaunchKernelGGL((bn_bwd_apply_kernel<T, GT>), dim3(grid_of(nq)), dim3(256), 0, st,        \
+  hipLaunchKernelGGL((bn_bwd_apply_kernel<T, GT>), dim3(grid_for(nq)), dim3(256), 0, st,        \
                      (const T*)x, (const GT*)dy, rows, C, scale, shift, nullptr, kbuf, dx,     \
                      accumulate_dx)
   if (dtype == CLSKD_BF16) {
@@ -1115,10 +1046,10 @@ extern "C" int clskd_nearest_down_sum(const void* g, int32_t B, int32_t F, int32
   CLSKD_CHECK_SHAPE(C % 4 == 0 && F >= Fr && T >= Tr, "nearest_down_sum: shape");
   const int64_t total = (int64_t)B * Fr * Tr * (C / 4);
   if (g_dtype == CLSKD_BF16)
-    hipLaunchKernelGGL(nearest_down_sum_kernel<__bf16>, dim3(grid_of(total)), dim3(256), 0,
+    hipLaunchKernelGGL(nearest_down_sum_kernel<__bf16>, dim3(grid_for(total)), dim3(256), 0,
                        as_stream(stream), (const __bf16*)g, B, F, T, Fr, Tr, C, out, accumulate);
   else
-    hipLaunchKernelGGL(nearest_down_sum_kernel<float>, dim3(grid_of(total)), dim3(256), 0,
+    hipLaunchKernelGGL(nearest_down_sum_kernel<float>, dim3(grid_for(total)), dim3(256), 0,
                        as_stream(stream), (const float*)g, B, F, T, Fr, Tr, C, out, accumulate);
   CLSKD_LAUNCH_CHECK("nearest_down_sum");
   return CLSKD_OK;
@@ -1153,7 +1084,7 @@ extern "C" int clskd_spkd_bn_bwd(const void* raw, int32_t dtype, int64_t sB, int
   float* k = reinterpret_cast<float*>(work + (int64_t)nblk * C * 3);
   const int64_t ppb = cdiv(P, nblk);
   const int64_t nq = P * (C / 4);
-  const unsigned ga = grid_of(nq, 16384);
+  const unsigned ga = grid_for(nq, 16384);
 #define SBB_RED(T_, BM_)                                                                            \
   do {                                                                                              \
     if (B == BM_)                                                                                   \
@@ -1200,7 +1131,7 @@ extern "C" int clskd_ola_bwd(const float* frames, const float* window, const flo
                              int32_t clamp, float* dframes, void* stream) {
   CLSKD_CHECK_ARG(frames && window && dwav && dframes, "ola_bwd: null pointer");
   const int64_t total = (int64_t)B * T * win;
-  hipLaunchKernelGGL(ola_bwd_kernel, dim3(grid_of(total)), dim3(256), 0, as_stream(stream), frames,
+  hipLaunchKernelGGL(ola_bwd_kernel, dim3(grid_for(total)), dim3(256), 0, as_stream(stream), frames,
                      window, dwav, B, T, win, hop, out_len, trim, clamp, dframes);
   CLSKD_LAUNCH_CHECK("ola_bwd");
   return CLSKD_OK;
@@ -1212,8 +1143,8 @@ extern "C" int clskd_frame_pad_bwd(const float* dxp, int32_t B, int32_t L, int32
   CLSKD_CHECK_ARG(dxp && dx, "frame_pad_bwd: null pointer");
   CLSKD_CHECK_SHAPE(mode == 0 || (mode == 1 && pad < L), "frame_pad_bwd: reflect pad %d >= L %d", pad, L);
   const int64_t total = (int64_t)B * L;
-  hipLaunchKernelGGL(frame_pad_bwd_kernel, dim3(grid_of(total)), dim3(256), 0, as_stream(stream), dxp,
-                     B, L, pad, Lp, mode, dx, ldx, accumulate);
+  hipLaunchKernelGGL(frame_pad_bwd_kernel, dim3(grid_for(total)), dim3(256), 0, as_stream(stream),
+                     dxp, B, L, pad, Lp, mode, dx, ldx, accumulate);
   CLSKD_LAUNCH_CHECK("frame_pad_bwd");
   return CLSKD_OK;
 }
@@ -1223,7 +1154,7 @@ extern "C" int clskd_stft_mag_loss_bwd(const float* X, const float* Y, int64_t r
                                        void* stream) {
   CLSKD_CHECK_ARG(X && Y && dX, "stft_mag_loss_bwd: null pointer");
   CLSKD_CHECK_SHAPE(ld >= 2 * nbins && ldd >= 2 * nbins, "stft_mag_loss_bwd: ld");
-  hipLaunchKernelGGL(stft_mag_loss_bwd_kernel, dim3(grid_of(rows * ldd)), dim3(256), 0,
+  hipLaunchKernelGGL(stft_mag_loss_bwd_kernel, dim3(grid_for(rows * ldd)), dim3(256), 0,
                      as_stream(stream), X, Y, rows, ld, nbins, scale, dX, ldd);
   CLSKD_LAUNCH_CHECK("stft_mag_loss_bwd");
   return CLSKD_OK;
@@ -1232,7 +1163,7 @@ extern "C" int clskd_stft_mag_loss_bwd(const float* X, const float* Y, int64_t r
 extern "C" int clskd_complex_combine_bwd(const float* dreal, const float* dimag, int32_t B,
                                          int64_t n, float* dh, void* stream) {
   CLSKD_CHECK_ARG(dreal && dimag && dh, "complex_combine_bwd: null pointer");
-  hipLaunchKernelGGL(complex_combine_bwd_kernel, dim3(grid_of((int64_t)B * n)), dim3(256), 0,
+  hipLaunchKernelGGL(complex_combine_bwd_kernel, dim3(grid_for((int64_t)B * n)), dim3(256), 0,
                      as_stream(stream), dreal, dimag, B, n, dh);
   CLSKD_LAUNCH_CHECK("complex_combine_bwd");
   return CLSKD_OK;

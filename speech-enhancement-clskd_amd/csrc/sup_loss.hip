@@ -21,6 +21,7 @@
 #include <algorithm>
 
 #include "common.h"
+#include "reduce.h"
 
 namespace clskd {
 
@@ -93,18 +94,6 @@ __global__ __launch_bounds__(256) void wave_sums_kernel(const float* __restrict_
   }
 }
 
-// fixed-order block sum of one double per thread (256 threads)
-__device__ __forceinline__ double block_sum_256(double v, double* red) {
-  __syncthreads();
-  red[threadIdx.x] = v;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-    __syncthreads();
-  }
-  return red[0];
-}
-
 // residual energy sum (e - a r)^2 around D: Er = sum r^2, X = sum r e, D = sum (e - r)^2
 __device__ __forceinline__ double resid(double D, double X, double Er, double a) {
   const double u = 1.0 - a;
@@ -119,7 +108,6 @@ __global__ __launch_bounds__(256) void wave_finalize_kernel(const double* __rest
                                                             double* __restrict__ rows,
                                                             float* __restrict__ out,
                                                             float* __restrict__ coef) {
-  __shared__ double red[256];
   const double eps = 1e-8;
   double sD = 0, sSdr = 0, sSnr = 0, sR3 = 0, sR4 = 0;
   for (int b = threadIdx.x; b < B; b += 256) {
@@ -145,11 +133,10 @@ __global__ __launch_bounds__(256) void wave_finalize_kernel(const double* __rest
       sR4 += a * a * A / resid(D, C, A, a) + eps;
     }
   }
-  const double tD = block_sum_256(sD, red);
-  const double tSdr = block_sum_256(sSdr, red);
-  const double tSnr = block_sum_256(sSnr, red);
-  const double R3 = block_sum_256(sR3, red) / (double)B;
-  const double R4 = block_sum_256(sR4, red) / (double)B;
+  double tot[5] = {sD, sSdr, sSnr, sR3, sR4};
+  block_tree_sum<5>(tot);
+  const double tD = tot[0], tSdr = tot[1], tSnr = tot[2];
+  const double R3 = tot[3] / (double)B, R4 = tot[4] / (double)B;
   const double invB = 1.0 / (double)B, invN = 1.0 / ((double)B * (double)L);
   if (threadIdx.x == 0) {
     const double l[5] = {tD * invN, -tSdr * invB, -tSnr * invB, -LOG10_K * log(R3 + eps),
@@ -381,7 +368,6 @@ __global__ __launch_bounds__(256) void mel_fwd_kernel(const float* __restrict__ 
   float* mc = reinterpret_cast<float*>(smem);
   float* me = mc + MEL_ROWS * MEL_NB;
   double* delta = reinterpret_cast<double*>(me + MEL_ROWS * MEL_NB);
-  __shared__ double red[256];
   const MelRange g = mel_range(T);
   const int b = blockIdx.y;
   for (int i = g.nrows * MEL_NB + threadIdx.x; i < MEL_ROWS * MEL_NB; i += 256) mc[i] = me[i] = 0.f;
@@ -392,7 +378,7 @@ __global__ __launch_bounds__(256) void mel_fwd_kernel(const float* __restrict__ 
   __syncthreads();
   double v = 0;
   if ((int)threadIdx.x < 3 * g.nrows) v = mel_rowval(delta, threadIdx.x / 3, threadIdx.x % 3);
-  const double tot = block_sum_256(v, red);
+  const double tot = block_tree_sum(v);
   if (threadIdx.x == 0) partial[(int64_t)b * gridDim.x + blockIdx.x] = tot;
 }
 
@@ -400,10 +386,9 @@ __global__ __launch_bounds__(256) void mel_fwd_kernel(const float* __restrict__ 
 __global__ __launch_bounds__(256) void mel_finalize_kernel(const double* __restrict__ partial,
                                                            int64_t n, double count, float scale,
                                                            int accumulate, float* out2) {
-  __shared__ double red[256];
   double s = 0;
   for (int64_t i = threadIdx.x; i < n; i += 256) s += partial[i];
-  const double tot = block_sum_256(s, red);
+  const double tot = block_tree_sum(s);
   if (threadIdx.x == 0) {
     const float mean = (float)(tot / count);
     const float v = (float)((double)scale * (tot / count));

@@ -1,4 +1,5 @@
-"""GPU: the three kernels of csrc/mini_bwd.hip against the float64 closed forms of
+"""GPU: the three kernels of the DCCRNet_mini backward (csrc/mini_bwd.hip; the OnReIm BatchNorm
+pair is clskd_bn_bwd_reim in csrc/norm_bwd.hip) against the float64 closed forms of
 tests/mini_train_ref.py, under the suite's one tolerance rule (tests/kernel_refs.py:tolerance):
 every element within 8 * e32 + 4 * 2^-24 * max|ref64|, e32 the distance of the same torch
 expression in float32 from float64; sums of float32 terms with the sum of the terms' magnitudes
@@ -91,12 +92,17 @@ def _bn_case(rows, C, seed):
     return x, dy, gamma, beta, alpha, keep
 
 
-@pytest.mark.parametrize("rows,C", [(7, 8), (1030, 16), (4099, 64)])
+BN_SHAPES = [(7, 8), (1030, 16), (4099, 64), (9, 4), (1030, 24), (515, 40)]
+
+
+@pytest.mark.parametrize("rows,C", BN_SHAPES)
 @pytest.mark.parametrize("acc_dx,acc_p", [(False, False), (True, False), (False, True), (True, True)])
 def test_bn_bwd_reim_against_fp64(rows, C, acc_dx, acc_p):
     """Slopes 0.25 (re half) and 0.05 (im half): one slope for both halves fails.  One block, a
-    ragged pair of blocks and nine blocks of the reduce; accumulate_dx / accumulate_params each
-    on and off (onto seeded buffers)."""
+    ragged pair of blocks and nine blocks of the reduce; C = 4 (one quad per row, a quad that
+    spans both halves), C = 24 and C = 40 (256 is no multiple of the quads per row: idle threads
+    behind the reduce's row-lane guard); accumulate_dx / accumulate_params each on and off (onto
+    seeded buffers)."""
     from clskd import ops
     x, dy, gamma, beta, alpha, keep = _bn_case(rows, C, 7 * rows + C)
     sc, sh, mean, var = M.bn_coefficients(x.double(), gamma.double(), beta.double())
@@ -128,6 +134,37 @@ def test_bn_bwd_reim_against_fp64(rows, C, acc_dx, acc_p):
         b = p.double() if acc_p else 0.0
         _check(f"{tag}/{name}", got, r64[k] + b, (r32[k].double() + b) if acc_p else r32[k],
                scale=mag + (p.double().abs() if acc_p else 0.0))
+
+
+@pytest.mark.parametrize("rows,C", BN_SHAPES)
+@pytest.mark.parametrize("acc", [False, True])
+def test_bn_bwd_reim_equal_slopes_is_bn_bwd(rows, C, acc):
+    """With one slope for both halves the OnReIm entry is clskd_bn_bwd: dx, dgamma and dbeta
+    bit for bit (accumulating onto seeded buffers or not), and dalpha_re + dalpha_im = dalpha to
+    three float32 roundings (the two halves' and their sum's, each <= 2^-24 relative: within
+    2 * 2^-24 * (|dalpha_re| + |dalpha_im|); the bound carries a factor 2 of margin).  The slope
+    gradients start from zero in both modes, so an accumulating call adds nothing to that count."""
+    from clskd import ops
+    x, dy, gamma, beta, _, _ = _bn_case(rows, C, 7 * rows + C)
+    sc, sh, mean, var = M.bn_coefficients(x.double(), gamma.double(), beta.double())
+    dv = lambda t: t.float().to(DEV).contiguous()  # noqa: E731
+    args = [dv(t) for t in (x, dy, sc, sh, mean, var)]
+    g = torch.Generator().manual_seed(5)
+    dx0, dg0, db0 = torch.randn(rows, C, generator=g), torch.randn(C, generator=g), torch.randn(C, generator=g)
+    outs = []
+    for fn, alpha in ((ops.bn_bwd_reim, [0.25, 0.25]), (ops.bn_bwd, [0.25])):
+        dx, dgam, dbet = dx0.clone().to(DEV), dg0.clone().to(DEV), db0.clone().to(DEV)
+        dalp = torch.zeros(len(alpha), device=DEV)
+        fn(*args, 1e-5, dv(gamma), torch.tensor(alpha, device=DEV), dx, dgam, dbet, dalp,
+           accumulate_dx=acc, accumulate_params=acc)
+        outs.append((dx, dgam, dbet, dalp))
+    torch.cuda.synchronize()
+    (dx2, dg2, db2, da2), (dx1, dg1, db1, da1) = outs
+    assert torch.equal(dx2, dx1) and torch.equal(dg2, dg1) and torch.equal(db2, db1)
+    da2, da1 = da2.double().cpu(), da1.double().cpu()
+    err, tol = float((da2.sum() - da1[0]).abs()), float(4 * 2.0 ** -24 * da2.abs().sum())
+    print(f"MINIK bn_bwd_reim=bn_bwd/r{rows}C{C}a{int(acc)}/dalpha err={err:.3e} tol={tol:.3e}")
+    assert err <= tol, (err, tol)
 
 
 # ------------------------------------------------------------------------------------------
