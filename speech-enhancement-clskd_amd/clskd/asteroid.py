@@ -24,7 +24,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from . import ops
+from . import clstm, ops
 from ._lib import check, ptr
 from .ops import OutMap, Seg, SegGeom, seg_bftc
 
@@ -338,36 +338,10 @@ class DCCRNet_mini(nn.Module):
         Ch = C6 // 2
         rnn = self.masker.encoders[-1].rnn
         H = rnn.rnns[0].re_module.rnn.hidden_size
-        r_in = None
-        for li in range(len(rnn.rnns)):
-            wp, bias, whh = self._lstm_w(li)
-            gx = torch.empty(2, B, Ti, 8 * H, **f32)
-            for half in range(2):
-                if li == 0:
-                    segs, taps = [seg_bftc(e6, c0=half * Ch, C=Ch)], [(f, 0) for f in range(D4)]
-                else:
-                    segs, taps = [Seg(r_in[half], 0, SegGeom(H, Ti * H, 0, H, 1, Ti))], [(0, 0)]
-                ops.conv(segs, taps, B, 1, Ti, 8 * H, wp, bias, gx[half],
-                         OutMap(Ti * 8 * H, 0, 8 * H))
-            hs = torch.empty(2, 2 * B, Ti, H, **f32)
-            # taped: the recurrence leaves the gate pre-activations in gx (lstm_bwd's `pre`) and
-            # the cell states in `cells`
-            pre = tape is not None and ops.lstm_pre_capable(H)
-            cells = None
-            if pre:
-                cells = torch.empty(2 * 2 * B * Ti * H, **f32)
-                ops.lstm_recurrent_pre(gx, 4 * H, Ti * 8 * H, 8 * H, whh, 2, 2 * B, Ti, H, hs,
-                                       2 * B * Ti * H, Ti * H, H, cbuf=cells)
-            else:
-                ops.lstm_recurrent(gx, 4 * H, Ti * 8 * H, 8 * H, whh, 2, 2 * B, Ti, H, hs,
-                                   2 * B * Ti * H, Ti * H, H)
-            if tape is not None:
-                tape.setdefault("lstm", []).append(dict(gx=gx, hs=hs, r_in=r_in, pre=pre,
-                                                        cells=cells))
-            ro = torch.empty(B, Ti, H, **f32)
-            io = torch.empty(B, Ti, H, **f32)
-            ops.complex_combine(hs[0, :B], hs[1, B:], hs[0, B:], hs[1, :B], ro, io)
-            r_in = (ro, io)
+        in0 = [([seg_bftc(e6, c0=half * Ch, C=Ch)], [(f, 0) for f in range(D4)])
+               for half in range(2)]
+        r_in = clstm.forward(in0, lambda li, segs: self._lstm_w(li), len(rnn.rnns), B, Ti, H, f32,
+                             tape=tape)[-1]
         wre, bre, wim, bim = self._lin_w()
         rnn_out = torch.empty(B, D4, Ti, C6, **f32)
         segs = [Seg(r_in[h], 0, SegGeom(H, Ti * H, 0, H, 1, Ti)) for h in range(2)]

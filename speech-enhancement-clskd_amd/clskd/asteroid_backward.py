@@ -13,7 +13,7 @@ passes over one tape give the same bits.  The filterbanks are buffers and are no
 import torch
 
 from . import backward as bw
-from . import ops
+from . import clstm, ops
 from .asteroid import DCCRNet_mini
 from .backward import _cbias_fn, _dec_dgrad_w, _empty, _enc_pack_fn, _scatter, _tw, unpack_maps
 from .ops import OutMap, Seg, SegGeom, seg_bftc
@@ -190,76 +190,9 @@ def _mini_backward(m, tape, d_wav, pg, acc, B, T, L, spec, enc, mask, dev):
                  OutMap(Ti * H, 0, H), mfma_only=True)
 
     # ---------------- two complex LSTM layers, reverse
-    for li in range(len(rnn.rnns) - 1, -1, -1):
-        lt = tape["lstm"][li]
-        gx, hs = lt["gx"], lt["hs"]
-        R, I = rnn.rnns[li].re_module.rnn, rnn.rnns[li].im_module.rnn
-        wp, _, whh = m._lstm_w(li)
-        dh = _empty((2, 2 * B, Ti, H), dev)
-        ops.complex_combine_bwd(d_out[0], d_out[1], dh)
-        whp = _tw(("mini_whh_p", id(m), li), whh,
-                  lambda: torch.stack([ops.pack_weight(whh[ws].unsqueeze(1), H) for ws in (0, 1)]))
-        if not lt["pre"]:
-            # gate pre-activations gx + h_{t-1} W_hh^T over the saved history, in place in gx
-            # (once per tape: a second backward over it finds them there)
-            for ws in range(2):
-                hseg = Seg(hs, ws * 2 * B * Ti * H, SegGeom(H, Ti * H, 0, H, 1, Ti))
-                ops.conv([hseg], [(0, -1)], 2 * B, 1, Ti, 4 * H, whp[ws], None, gx,
-                         OutMap(Ti * 8 * H, 0, 8 * H), out_offset=ws * 4 * H, accumulate=True)
-            lt["pre"] = True
-        dg = _empty((2, B, Ti, 8 * H), dev)
-        st = (4 * H, Ti * 8 * H, 8 * H)
-        ops.lstm_bwd(gx, st, dh, (2 * B * Ti * H, Ti * H, H), whh, 2, 2 * B, Ti, H, dg, st,
-                     cells=lt.get("cells"))
-        # W_hh gradient per weight set: rows (seq, t) x the shifted history h_{t-1}
-        Kh = whp.shape[2]
-        dwhh = _empty((2, 4 * H, Kh), dev)
-        for ws in range(2):
-            hseg = Seg(hs, ws * 2 * B * Ti * H, SegGeom(H, Ti * H, 0, H, 1, Ti))
-            ops.conv_wgrad([hseg], [(0, -1)], 2 * B, 1, Ti, 4 * H, dg, OutMap(Ti * 8 * H, 0, 8 * H),
-                           dwhh[ws], dy_offset=ws * 4 * H)
-        _scatter(dwhh, unpack_maps(("whh", H, Kh), lambda a, b: torch.cat([
-            torch.cat([a, a.new_zeros(4 * H, Kh - H)], 1), torch.cat([b, b.new_zeros(4 * H, Kh - H)], 1)], 0),
-            [(4 * H, H), (4 * H, H)], Kh, dev), [pg.get(R.weight_hh_l0), pg.get(I.weight_hh_l0)], acc)
-        # W_ih / gate-bias gradients (the two input halves accumulate) and the input gradient
-        dwih = _empty(wp.shape, dev)
-        dbias = _empty((8 * H,), dev)
-        nxt = [_empty((B, Ti, H), dev), _empty((B, Ti, H), dev)] if li > 0 else None
-        for half in range(2):
-            if li == 0:
-                segs = [seg_bftc(e6, c0=half * Ch, C=Ch)]
-                taps = [(f, 0) for f in range(D4)]
-            else:
-                segs = [Seg(lt["r_in"][half], 0, SegGeom(H, Ti * H, 0, H, 1, Ti))]
-                taps = [(0, 0)]
-            ops.conv_wgrad(segs, taps, B, 1, Ti, 8 * H, dg[half], OutMap(Ti * 8 * H, 0, 8 * H), dwih,
-                           dbias, accumulate=half == 1)
-            gseg = [Seg(dg[half], 0, SegGeom(8 * H, Ti * 8 * H, 0, 8 * H, 1, Ti))]
-            if li == 0:
-                wti = _tw(("mini_ih_t", id(m), li), wp, lambda: ops.pack_weight(
-                    wp[:, :D4 * Ch].t().contiguous().unsqueeze(1), 8 * H))
-                ops.conv(gseg, [(0, 0)], B, 1, Ti, D4 * Ch, wti, None, g_enc[-1],
-                         OutMap(D4 * Ti * C6, 0, C6, Ti * C6, 1, Ch), out_offset=half * Ch,
-                         accumulate=True)
-            else:
-                wti = _tw(("mini_ih_t", id(m), li), wp, lambda: ops.pack_weight(
-                    wp[:, :H].t().contiguous().unsqueeze(1), 8 * H))
-                ops.conv(gseg, [(0, 0)], B, 1, Ti, H, wti, None, nxt[half], OutMap(Ti * H, 0, H),
-                         mfma_only=True)
-        D = R.weight_ih_l0.shape[1]
-        if li == 0:
-            fn = lambda a, b, D=D: torch.cat([a, b], 0).reshape(8 * H, D // D4, D4).permute(0, 2, 1).reshape(8 * H, D)  # noqa: E731
-        else:
-            fn = lambda a, b: torch.cat([a, b], 0)  # noqa: E731
-        _scatter(dwih, unpack_maps(("mini_wih", li, H, D, D4), fn, [(4 * H, D), (4 * H, D)],
-                                   wp.shape[1], dev),
-                 [pg.get(R.weight_ih_l0), pg.get(I.weight_ih_l0)], acc)
-        # bias_ih and bias_hh both receive the gate-bias gradient
-        bmaps = unpack_maps(("lstm_b", H), lambda a, b, c, e: torch.cat([a + b, c + e]).reshape(-1, 1),
-                            [(4 * H,)] * 4, 1, dev)
-        _scatter(dbias, bmaps, [pg.get(R.bias_ih_l0), pg.get(R.bias_hh_l0), pg.get(I.bias_ih_l0),
-                                pg.get(I.bias_hh_l0)], acc)
-        d_out = nxt
+    in0 = [([seg_bftc(e6, c0=half * Ch, C=Ch)], [(f, 0) for f in range(D4)]) for half in range(2)]
+    clstm.backward(d_out, tape, m._lstm_w,
+                   [(r.re_module.rnn, r.im_module.rnn) for r in rnn.rnns], in0, g_enc[-1], m, pg, acc)
 
     # ---------------- encoders 6..1 (5x2 kernel, F stride 2, no time padding: T shrinks by one
     # per block, so a data gradient reads zeros outside the block's [0, To)), reverse

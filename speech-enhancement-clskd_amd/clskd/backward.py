@@ -27,7 +27,7 @@ import weakref
 import numpy as np
 import torch
 
-from . import ops
+from . import clstm, ops
 from .ops import OutMap, Seg, SegGeom, seg_bftc
 
 f32 = torch.float32
@@ -475,75 +475,11 @@ def dccrn_backward(m, tape, enc, dec, dec_in, lstm_io, g, pg, acc_params=False, 
         dseg = Seg(g["dec_in"], half * Ch, SegGeom(Ch, D4 * T * C6, T * C6, C6, D4, T))
         ops.conv([dseg], [(f, 0) for f in range(D4)], B, 1, T, H, wt, None, d_out[half],
                  OutMap(T * H, 0, H), mfma_only=True)
-    for li in range(m.hidden_layers - 1, -1, -1):
-        lt = tape["lstm"][li]
-        gx, hs = lt["gx"], lt["hs"]
-        mod = m.enhance[li]
-        R, I = mod.real_lstm, mod.imag_lstm
-        wp, bias, whh = m._lstm_w(li, "fp32")[:3]
-        dh = _empty((2, 2 * B, T, H), dev)
-        ops.complex_combine_bwd(d_out[0], d_out[1], dh)
-        # gate pre-activations: gx + h_{t-1} W_hh^T over the saved history (in place in gx) —
-        # unless the taped forward's recurrence left them there (clskd_lstm_recurrent_pre)
-        whp = _tw(("whh_p", id(m), li), whh,
-                  lambda: torch.stack([ops.pack_weight(whh[ws].unsqueeze(1), H) for ws in (0, 1)]))
-        if not lt.get("pre", False):
-            for ws in range(2):
-                hseg = Seg(hs, ws * 2 * B * T * H, SegGeom(H, T * H, 0, H, 1, T))
-                ops.conv([hseg], [(0, -1)], 2 * B, 1, T, 4 * H, whp[ws], None, gx,
-                         OutMap(T * 8 * H, 0, 8 * H), out_offset=ws * 4 * H, accumulate=True)
-        dg = _empty((2, B, T, 8 * H), dev)
-        st = (4 * H, T * 8 * H, 8 * H)
-        ops.lstm_bwd(gx, st, dh, (2 * B * T * H, T * H, H), whh, 2, 2 * B, T, H, dg, st,
-                     cells=lt.get("cells"))
-        # W_hh gradient per weight set: rows (seq, t) x history h_{t-1}
-        Kh = whp.shape[2]
-        dwhh = _empty((2, 4 * H, Kh), dev)
-        for ws in range(2):
-            hseg = Seg(hs, ws * 2 * B * T * H, SegGeom(H, T * H, 0, H, 1, T))
-            ops.conv_wgrad([hseg], [(0, -1)], 2 * B, 1, T, 4 * H, dg, OutMap(T * 8 * H, 0, 8 * H),
-                           dwhh[ws], dy_offset=ws * 4 * H)
-        _scatter(dwhh, unpack_maps(("whh", H, Kh), lambda a, b: torch.cat([
-            torch.cat([a, a.new_zeros(4 * H, Kh - H)], 1), torch.cat([b, b.new_zeros(4 * H, Kh - H)], 1)], 0),
-            [(4 * H, H), (4 * H, H)], Kh, dev), [pg.get(R.weight_hh_l0), pg.get(I.weight_hh_l0)],
-            acc_params)
-        # W_ih / bias gradients (the two input halves accumulate) and the input gradient
-        dwih = _empty(wp.shape, dev)
-        dbias = _empty((8 * H,), dev)
-        nxt = [_empty((B, T, H), dev), _empty((B, T, H), dev)] if li > 0 else None
-        for half in range(2):
-            if li == 0:
-                segs = [seg_bftc(enc[-1], c0=half * Ch, C=Ch)]
-                taps = [(f, 0) for f in range(D4)]
-            else:
-                segs = [Seg(lt["r_in"][half], 0, SegGeom(H, T * H, 0, H, 1, T))]
-                taps = [(0, 0)]
-            ops.conv_wgrad(segs, taps, B, 1, T, 8 * H, dg[half], OutMap(T * 8 * H, 0, 8 * H), dwih,
-                           dbias, accumulate=half == 1)
-            gseg = [Seg(dg[half], 0, SegGeom(8 * H, T * 8 * H, 0, 8 * H, 1, T))]
-            if li == 0:
-                wt = _tw(("ih_t", id(m), li), wp, lambda: ops.pack_weight(
-                    wp[:, :D4 * Ch].t().contiguous().unsqueeze(1), 8 * H))
-                ops.conv(gseg, [(0, 0)], B, 1, T, D4 * Ch, wt, None, g["enc"][-1],
-                         OutMap(D4 * T * C6, 0, C6, T * C6, 1, Ch), out_offset=half * Ch,
-                         accumulate=True)
-            else:
-                wt = _tw(("ih_t", id(m), li), wp, lambda: ops.pack_weight(
-                    wp[:, :H].t().contiguous().unsqueeze(1), 8 * H))
-                ops.conv(gseg, [(0, 0)], B, 1, T, H, wt, None, nxt[half], OutMap(T * H, 0, H),
-                         mfma_only=True)
-        D = R.weight_ih_l0.shape[1]
-        if li == 0:
-            fn = lambda a, b: torch.cat([a, b], 0).reshape(8 * H, D // 4, 4).permute(0, 2, 1).reshape(8 * H, D)
-        else:
-            fn = lambda a, b: torch.cat([a, b], 0)
-        _scatter(dwih, unpack_maps(("wih", li, H, D), fn, [(4 * H, D), (4 * H, D)], wp.shape[1], dev),
-                 [pg.get(R.weight_ih_l0), pg.get(I.weight_ih_l0)], acc_params)
-        bmaps = unpack_maps(("lstm_b", H), lambda a, b, c, e: torch.cat([a + b, c + e]).reshape(-1, 1),
-                            [(4 * H,)] * 4, 1, dev)
-        _scatter(dbias, bmaps, [pg.get(R.bias_ih_l0), pg.get(R.bias_hh_l0), pg.get(I.bias_ih_l0),
-                                pg.get(I.bias_hh_l0)], acc_params)
-        d_out = nxt
+    in0 = [([seg_bftc(enc[-1], c0=half * Ch, C=Ch)], [(f, 0) for f in range(D4)])
+           for half in range(2)]
+    clstm.backward(d_out, tape, lambda li: m._lstm_w(li, "fp32")[:3],
+                   [(mod.real_lstm, mod.imag_lstm) for mod in m.enhance], in0, g["enc"][-1], m, pg,
+                   acc_params)
 
     # ---------------- encoder (DCCRN.py:171-176), reverse
     for i in range(nl - 1, -1, -1):

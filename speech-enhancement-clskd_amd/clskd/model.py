@@ -19,6 +19,7 @@ import torch
 import torch.nn as nn
 from scipy.signal import get_window
 
+from . import clstm
 from . import config as cfg
 from . import ops
 from .ops import OutMap, Seg, SegGeom, seg_bftc
@@ -785,46 +786,16 @@ class DCCRN(nn.Module):
         act6 = enc[-1]
         D4 = act6.shape[1]
         H = self.rnn_units // 2
-        r_in = None
-        lstm_io = []
-        for li in range(self.hidden_layers):
-            gx = torch.empty(2, B, T, 8 * H, **f32)
-            for half in range(2):
-                if li == 0:
-                    segs = [seg_bftc(act6, c0=half * Ch, C=Ch)]
-                    taps = [(f, 0) for f in range(D4)]
-                else:
-                    src = r_in[half]
-                    segs = [Seg(src, 0, SegGeom(H, T * H, 0, H, 1, T))]
-                    taps = [(0, 0)]
-                packs = self._lstm_w(li, self._cmp(segs, len(taps) * segs[0].geom.C))
-                wp, bias, whh = packs[:3]
-                ops.conv(segs, taps, B, 1, T, 8 * H, wp, bias, gx[half],
-                         OutMap(T * 8 * H, 0, 8 * H))
-            hs = torch.empty(2, 2 * B, T, H, **f32)
-            # taped: the recurrence leaves the gate pre-activations in gx (the backward's `pre`)
-            pre = tape is not None and ops.lstm_pre_capable(H)
-            cells = None
-            if pre:  # ... and its cell states (the backward then skips its cell-state scan)
-                cells = torch.empty(2 * 2 * B * T * H, **f32) if _LSTM_CELLS else None
-                ops.lstm_recurrent_pre(gx, 4 * H, T * 8 * H, 8 * H, whh, 2, 2 * B, T, H, hs,
-                                       2 * B * T * H, T * H, H, cbuf=cells)
-            else:
-                ops.lstm_recurrent(gx, 4 * H, T * 8 * H, 8 * H, whh, 2, 2 * B, T, H, hs,
-                                   2 * B * T * H, T * H, H)
-            if tape is not None:
-                tape.setdefault("lstm", []).append(dict(gx=gx, hs=hs, r_in=r_in, pre=pre,
-                                                        cells=cells))
-            # a 16-bit model (the frozen teacher in precision 'mixed' / 'fp16') stores the layer
-            # output as the 16-bit operand of the next layer's input GEMM and the projection
-            # (one rounding, as every other teacher activation); fp32 models and taped
-            # (backward) forwards keep fp32
-            lo = act if (self.compute != "fp32" and tape is None) else f32
-            ro = torch.empty(B, T, H, **lo)
-            io = torch.empty(B, T, H, **lo)
-            ops.complex_combine(hs[0, :B], hs[1, B:], hs[0, B:], hs[1, :B], ro, io)
-            r_in = (ro, io)
-            lstm_io.append((ro, io))
+        # a 16-bit model (the frozen teacher in precision 'mixed' / 'fp16') stores the layer
+        # output as the 16-bit operand of the next layer's input GEMM and the projection
+        # (one rounding, as every other teacher activation); fp32 models and taped
+        # (backward) forwards keep fp32
+        lo = act if (self.compute != "fp32" and tape is None) else f32
+        in0 = [([seg_bftc(act6, c0=half * Ch, C=Ch)], [(f, 0) for f in range(D4)])
+               for half in range(2)]
+        lstm_io = clstm.forward(in0, lambda li, segs: self._lstm_w(li, self._cmp(segs))[:3],
+                                self.hidden_layers, B, T, H, lo, _LSTM_CELLS, tape)
+        r_in = lstm_io[-1]
         # projection into the decoder input [B][D4][T][C6] (DCCRN.py:188-199)
         dec_in = torch.empty(B, D4, T, C6, **act)
         m = self._layer_refs()["lstm"][self.hidden_layers - 1]

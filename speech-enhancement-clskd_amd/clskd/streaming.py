@@ -23,6 +23,7 @@ frame the decoder pipeline drains with zero frames (the offline decoder's out-of
 """
 import torch
 
+from . import clstm
 from . import config as cfg
 from . import ops
 from .model import refuse_cbn
@@ -161,24 +162,10 @@ class StreamingDCCRN:
                     self.ering[i][-1].copy_(dst)
             # ---- complex LSTMs (DCCRN.py:178-199), state carried across hops
             C6, Ch, D4 = m.kernel_num[-1], m.kernel_num[-1] // 2, self.D4
-            r_in = None
-            for li in range(m.hidden_layers):
-                packs = m._lstm_w(li, "fp32")
-                wp, bias, whh = packs[:3]
-                for half in range(2):
-                    if li == 0:
-                        # newest frame (slot 1) of the last encoder output's 2-frame ring
-                        segs = [_seg_tm(self.ering[nl - 1], 1, 1, half * Ch, Ch)]
-                        taps = [(f, 0) for f in range(D4)]
-                    else:
-                        segs = [Seg(r_in[half], 0, SegGeom(H, H, 0, H, 1, 1))]
-                        taps = [(0, 0)]
-                    ops.conv(segs, taps, B, 1, 1, 8 * H, wp, bias, self.gx[half], OutMap(8 * H, 0, 8 * H))
-                ops.lstm_cell(self.gx, 4 * H, 8 * H, whh, 2, 2 * B, H, self.h[li], self.c[li],
-                              2 * B * H, H, self.hs, 2 * B * H, H)
-                ro, io = self.rio[li]
-                ops.complex_combine(self.hs[0, :B], self.hs[1, B:], self.hs[0, B:], self.hs[1, :B], ro, io)
-                r_in = (ro, io)
+            in0 = [([_seg_tm(self.ering[nl - 1], 1, 1, half * Ch, Ch)], [(f, 0) for f in range(D4)])
+                   for half in range(2)]  # newest frame (slot 1) of the last encoder output's ring
+            r_in = clstm.hop(in0, lambda li, segs: m._lstm_w(li, "fp32")[:3], m.hidden_layers, B, H,
+                             self.gx, self.h, self.c, self.hs, self.rio)
             last = m.enhance[m.hidden_layers - 1]
             packs = m._lstm_w(m.hidden_layers - 1, "fp32")
             for half in range(2):
@@ -607,21 +594,10 @@ class StreamingDCCRNet_mini(_StreamingMini):
                     dst.zero_()
         # ---- complex LSTMs on frame u-6 (carried state), complex Linear -> transposed conv 0 input
         if live and u >= MINI_LOOKAHEAD:
-            r_in = None
-            for li in range(2):
-                wp, bias, whh = self.w_lstm[li]
-                for half in range(2):
-                    if li == 0:
-                        segs = [_seg_tm(self.ering[5], 1, 1, half * Ch, Ch)]
-                        taps = [(f, 0) for f in range(D4)]
-                    else:
-                        segs, taps = [Seg(r_in[half], 0, SegGeom(H, H, 0, H, 1, 1))], [(0, 0)]
-                    ops.conv(segs, taps, B, 1, 1, 8 * H, wp, bias, self.gx[half], OutMap(8 * H, 0, 8 * H))
-                ops.lstm_cell(self.gx, 4 * H, 8 * H, whh, 2, 2 * B, H, self.h[li], self.c[li],
-                              2 * B * H, H, self.hs, 2 * B * H, H)
-                ro, io = self.rio[li]
-                ops.complex_combine(self.hs[0, :B], self.hs[1, B:], self.hs[0, B:], self.hs[1, :B], ro, io)
-                r_in = (ro, io)
+            in0 = [([_seg_tm(self.ering[5], 1, 1, half * Ch, Ch)], [(f, 0) for f in range(D4)])
+                   for half in range(2)]
+            r_in = clstm.hop(in0, lambda li, segs: self.w_lstm[li], 2, B, H, self.gx, self.h, self.c,
+                             self.hs, self.rio)
             wre, bre, wim, bim = self.w_lin
             segs = [Seg(r_in[h], 0, SegGeom(H, H, 0, H, 1, 1)) for h in range(2)]
             for half, (w, b) in enumerate(((wre, bre), (wim, bim))):

@@ -222,6 +222,18 @@ __device__ __forceinline__ int xcd_tile(int bid, int nb) {
 
 __device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
 
+// LSTM gate nonlinearities on v_exp_f32 / v_rcp_f32 (~1 ulp each; the recurrence's fp32 rounding,
+// not these, dominates its error against the oracle).  One definition for the offline recurrence
+// (lstm.hip) and the fused streaming hops, so a stream of hops reproduces the offline sequence.
+__device__ __forceinline__ float sigm_fast(float x) {
+  return __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(-x * 1.4426950408889634f));
+}
+__device__ __forceinline__ float tanh_fast(float x) {
+  return 1.f - 2.f * __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(x * 2.8853900817779268f));
+}
+// the tanh of the g gate, on the sigmoid's instructions: 2 sigmoid(2x) - 1
+__device__ __forceinline__ float tanh_gate(float x) { return fmaf(2.f, sigm_fast(2.f * x), -1.f); }
+
 // scale/shift (and batch mean/var, running stats) of one channel from its totals.
 __device__ __forceinline__ void bn_channel_coeffs(int c, double S, double Q, int64_t rows,
                                                   const float* gamma, const float* beta, float eps,

@@ -24,17 +24,175 @@ __device__ __forceinline__ float dpp(float v) {
 constexpr int DPP_XOR1 = 0xB1;         // quad_perm [1,0,3,2]
 constexpr int DPP_XOR2 = 0x4E;         // quad_perm [2,3,0,1]
 constexpr int DPP_HALF_MIRROR = 0x141; // lane i <- lane 7-i within each 8-lane half-row
+constexpr int DPP_PAIR_HI = 0xF5;      // quad_perm [1,1,3,3]
 constexpr int DPP_BCAST1 = 0x55;       // quad_perm [1,1,1,1]
 constexpr int DPP_BCAST2 = 0xAA;       // quad_perm [2,2,2,2]
 constexpr int DPP_BCAST3 = 0xFF;       // quad_perm [3,3,3,3]
 
-// Gate nonlinearities on v_exp_f32 / v_rcp_f32 (~1 ulp each; the recurrence's fp32 rounding,
-// not these, dominates its error against the oracle).
-__device__ __forceinline__ float sigm_fast(float x) {
-  return __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(-x * 1.4426950408889634f));
+// ------------------------------------------------------------------------------------------
+// The recurrence core: the pieces the forward and backward kernels below are made of.  Lane
+// layout everywhere: the S (or NKS) lanes of hidden unit u are adjacent, lane = u * S + ks, so a
+// unit's group sits inside one DPP quad (S <= 4) or half-row (S = 8).  All helpers are force-
+// inlined and hold no state; gate order i, f, g, o (sigmoid, sigmoid, tanh, sigmoid).
+// (sigm_fast / tanh_fast / tanh_gate: common.h, shared with the streaming-hop kernels.)
+// ------------------------------------------------------------------------------------------
+
+// Sum over the S adjacent lanes of a unit group, in every lane of the group (butterfly: xor 1,
+// xor 2, then the half-row mirror for S = 8).  All 64 lanes must be active.
+template <int S>
+__device__ __forceinline__ float group_sum(float v) {
+  static_assert(S == 2 || S == 4 || S == 8, "lanes per unit");
+  v += dpp<DPP_XOR1>(v);
+  if constexpr (S >= 4) v += dpp<DPP_XOR2>(v);
+  if constexpr (S == 8) v += dpp<DPP_HALF_MIRROR>(v);
+  return v;
 }
-__device__ __forceinline__ float tanh_fast(float x) {
-  return 1.f - 2.f * __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(x * 2.8853900817779268f));
+
+// pre[gate] = (W_hh h(t-1)) of the lane's unit and gate, in every lane of the unit's group: the
+// lane's k-slice of the product (w: the unit's four gate rows restricted to the slice, packed pairs; hp: the slice of h(t-1) in LDS, 16-byte
+// aligned; the caller has made the writes of h(t-1) visible), then the group sum.  Two packed
+// accumulators per gate, even / odd float4 of the slice, summed at the end: the sum order of the
+// recurrence.
+// PIN: every h read is issued before the first FMA — the compiler split the 8 reads of H = 128
+// into three dependent groups (one register quad reused); the memory clobber keeps all reads
+// above the pins, and the pins make each value live at once (FMAs start as they arrive).  The
+// multi-wave kernel has it, the single-wave kernel does not.
+template <int KW, int S, bool PIN>
+__device__ __forceinline__ void unit_matvec(const float* hp, const f32x2l (&w)[4][KW / 2],
+                                            float (&pre)[4]) {
+  f32x4 hv[KW / 4];
+#pragma unroll
+  for (int j = 0; j < KW / 4; ++j) hv[j] = reinterpret_cast<const f32x4*>(hp)[j];
+  if constexpr (PIN) {
+#pragma unroll
+    for (int j = 0; j < KW / 4; ++j) asm volatile("" : "+v"(hv[j]) : : "memory");
+  }
+  f32x2l acc[4][2] = {};
+#pragma unroll
+  for (int j = 0; j < KW / 4; ++j) {
+    const f32x2l h01 = {hv[j][0], hv[j][1]}, h23 = {hv[j][2], hv[j][3]};
+#pragma unroll
+    for (int gt = 0; gt < 4; ++gt) {
+      acc[gt][j & 1] = __builtin_elementwise_fma(w[gt][2 * j], h01, acc[gt][j & 1]);
+      acc[gt][j & 1] = __builtin_elementwise_fma(w[gt][2 * j + 1], h23, acc[gt][j & 1]);
+    }
+  }
+#pragma unroll
+  for (int gt = 0; gt < 4; ++gt) {
+    const f32x2l a2 = acc[gt][0] + acc[gt][1];
+    pre[gt] = group_sum<S>(a2[0] + a2[1]);
+  }
+}
+
+// sigmoid(x), or tanh(x) = 2 sigmoid(2x) - 1 where th: one branch-free form for a lane-dependent
+// gate.
+__device__ __forceinline__ float gate_act(float x, bool th) {
+  const float k = th ? 2.f : 1.f;
+  return fmaf(k, sigm_fast(k * x), th ? -1.f : 0.f);
+}
+
+// Which gates a lane of a unit group owns (ga = its index in the group; lanes >= 4 of an 8-lane
+// group pass ga & 3 and duplicate lanes 0 .. 3):
+//   S >= 4: lane ga owns gate ga, with gate input g0;
+//   S == 2: lane 0 owns i (g0) and g (g1), lane 1 owns f (g0) and o (g1).
+// gate_preacts: pre[gate] = the group-summed W_hh h of the unit (equal in all its lanes) -> the
+// lane's own pre-activations pa (and pb for S == 2), gate inputs added.
+template <int S>
+__device__ __forceinline__ void gate_preacts(const float (&pre)[4], int ga, float g0, float g1,
+                                             float& pa, float& pb) {
+  if constexpr (S >= 4) {
+    const float p01 = (ga & 1) ? pre[1] : pre[0];
+    const float p23 = (ga & 1) ? pre[3] : pre[2];
+    pa = ((ga & 2) ? p23 : p01) + g0;
+  } else {
+    pa = (ga ? pre[1] : pre[0]) + g0;
+    pb = (ga ? pre[3] : pre[2]) + g1;
+  }
+}
+// gates_to_lane0: every lane activates its own gates (branch-free) and lane 0 of the group
+// receives all four by DPP; ig, fg, gg, og are meaningful in lane 0 of each group only.  All 64
+// lanes must be active.  S == 2: lane 0 of each pair reads lane 1 with one quad_perm [1,1,3,3]
+// (the multi-wave kernel used to form the same values from two broadcasts and a select).
+template <int S>
+__device__ __forceinline__ void gates_to_lane0(float pa, float pb, int ga, float& ig, float& fg,
+                                               float& gg, float& og) {
+  if constexpr (S >= 4) {
+    const float act = gate_act(pa, ga == 2);
+    ig = act;
+    fg = dpp<DPP_BCAST1>(act);
+    gg = dpp<DPP_BCAST2>(act);
+    og = dpp<DPP_BCAST3>(act);
+  } else {
+    const float a0 = sigm_fast(pa);
+    const float a1 = gate_act(pb, ga == 0);
+    ig = a0;
+    gg = a1;
+    fg = dpp<DPP_PAIR_HI>(a0);
+    og = dpp<DPP_PAIR_HI>(a1);
+  }
+}
+
+// The gate inputs of step t for lane `ga` (see gates_to_lane0): gp = the unit's column of gx,
+// rows of H floats per gate, gx_t floats per step.  t is clamped to T - 1, so the kernels'
+// two-steps-ahead prefetch may run past the end.
+template <int H, bool TWO>
+__device__ __forceinline__ void load_gate_inputs(const float* gp, int64_t gx_t, int T, int t, int ga,
+                                                 float& g0, float& g1) {
+  const float* q = gp + (int64_t)min(t, T - 1) * gx_t;
+  g0 = q[ga * H];
+  if constexpr (TWO) g1 = q[(ga + 2) * H];
+}
+
+// Backward phase 1: c_t = f c_{t-1} + i g from the saved pre-activations (pp: the unit's column,
+// rows of H per gate, p_t per step) into cp[t * H].  Serial over t.  A lane reads back only what
+// it wrote itself, so no barrier follows.
+template <int H>
+__device__ __forceinline__ void cell_scan(const float* __restrict__ pp, int64_t p_t, int T,
+                                          float* __restrict__ cp) {
+  float c = 0.f;
+#pragma unroll 4
+  for (int t = 0; t < T; ++t) {
+    const float* q = pp + (int64_t)t * p_t;
+    const float ig = sigm_fast(q[0]), fg = sigm_fast(q[H]);
+    const float gg = tanh_gate(q[2 * H]);
+    c = fg * c + ig * gg;
+    cp[(int64_t)t * H] = c;
+  }
+}
+
+// The operands of one backward step of a unit: its four gate pre-activations, c_t, c_{t-1}
+// (0 at t = 0) and dL/dh_t from above.  t in [0, T).
+struct BwdOp {
+  float q0, q1, q2, q3, cc, cpv, dhin;
+};
+template <int H>
+__device__ __forceinline__ void fetch_op(const float* __restrict__ pp, int64_t p_t, const float* cp,
+                                         const float* __restrict__ dp, int64_t d_t, int t, BwdOp& o) {
+  const float* q = pp + (int64_t)t * p_t;
+  o.q0 = q[0];
+  o.q1 = q[H];
+  o.q2 = q[2 * H];
+  o.q3 = q[3 * H];
+  o.cc = cp[(int64_t)t * H];
+  o.cpv = t > 0 ? cp[(int64_t)(t - 1) * H] : 0.f;
+  o.dhin = dp[(int64_t)t * d_t];
+}
+
+// Gate gradients of step t (w.r.t. the pre-activations) from its operands and dhr = the
+// recurrent part (W_hh^T da_{t+1})_u of dL/dh_t; dc carries dL/dc across steps (in: the part
+// from step t+1, out: the part for step t-1).
+__device__ __forceinline__ void gate_grads(const BwdOp& o, float dhr, float& dc, float& a_i,
+                                           float& a_f, float& a_g, float& a_o) {
+  const float ig = sigm_fast(o.q0), fg = sigm_fast(o.q1);
+  const float gg = tanh_gate(o.q2), og = sigm_fast(o.q3);
+  const float tc = tanh_fast(o.cc);
+  const float dht = o.dhin + dhr;
+  dc = fmaf(dht * og, 1.f - tc * tc, dc);
+  a_i = dc * gg * ig * (1.f - ig);
+  a_f = dc * o.cpv * fg * (1.f - fg);
+  a_g = dc * ig * (1.f - gg * gg);
+  a_o = dht * tc * og * (1.f - og);
+  dc *= fg;
 }
 
 // Thread layout (NKS*H threads): thread = (hidden unit u = tid / NKS, k-slice ks = tid % NKS).
@@ -48,7 +206,7 @@ __device__ __forceinline__ float tanh_fast(float x) {
 // cell.  h goes to an LDS history ring, flushed to `out` every CH steps with coalesced
 // workgroup stores; the step barrier waits for LDS only.  The projected inputs are prefetched
 // two steps ahead (named registers, loop unrolled by two).  Packed FMAs (v_pk_fma_f32).
-template <int H, int NKS, int DBG = 0>
+template <int H, int NKS>
 __global__ __launch_bounds__(NKS * H) void lstm_recurrent_kernel(
     const float* __restrict__ gx, int64_t gx_ws, int64_t gx_seq, int64_t gx_t,
     const float* __restrict__ whh, int T, float* __restrict__ out, int64_t o_ws, int64_t o_seq,
@@ -83,76 +241,13 @@ __global__ __launch_bounds__(NKS * H) void lstm_recurrent_kernel(
   const int ga = NKS >= 4 ? (ks & 3) : ks;
   const float* gp = gx + ws * gx_ws + seq * gx_seq + u;
   float* op = out + ws * o_ws + seq * o_seq;
-  auto load_g = [&](int t, float& g0, float& g1) {
-    const float* q = gp + (int64_t)min(t, T - 1) * gx_t;
-    g0 = DBG == 1 ? 0.1f : q[ga * H];
-    if constexpr (NKS == 2) g1 = DBG == 1 ? 0.1f : q[(ga + 2) * H];
-  };
-  float ga0 = 0.f, ga1 = 0.f, gb0 = 0.f, gb1 = 0.f;
-  load_g(0, ga0, ga1);
-  load_g(1, gb0, gb1);
-  __syncthreads();
 
   auto step = [&](int t, float g0, float g1) {
-    const float* hp = hist[(t + 2 * CH - 1) % (2 * CH)] + ks * KW;
-    f32x4 hv[KW / 4];
-#pragma unroll
-    for (int j = 0; j < KW / 4; ++j) hv[j] = reinterpret_cast<const f32x4*>(hp)[j];
-    // every h read issued before the first FMA: the compiler split the 8 reads of H = 128 into
-    // three dependent groups (one register quad reused); the memory clobber keeps all reads
-    // above the pins, and the pins make each value live at once (FMAs start as they arrive)
-#pragma unroll
-    for (int j = 0; j < KW / 4; ++j) asm volatile("" : "+v"(hv[j]) : : "memory");
-    f32x2l acc[4][2] = {};
-#pragma unroll
-    for (int j = 0; j < KW / 4; ++j) {
-      const f32x2l h01 = {hv[j][0], hv[j][1]}, h23 = {hv[j][2], hv[j][3]};
-#pragma unroll
-      for (int gt = 0; gt < 4; ++gt) {
-        acc[gt][j & 1] = __builtin_elementwise_fma(w[gt][2 * j], h01, acc[gt][j & 1]);
-        acc[gt][j & 1] = __builtin_elementwise_fma(w[gt][2 * j + 1], h23, acc[gt][j & 1]);
-      }
-    }
     float pre[4];
-#pragma unroll
-    for (int gt = 0; gt < 4; ++gt) {  // NKS-lane group sum
-      const f32x2l a2 = acc[gt][0] + acc[gt][1];
-      float v = a2[0] + a2[1];
-      v += dpp<DPP_XOR1>(v);
-      if constexpr (NKS >= 4) v += dpp<DPP_XOR2>(v);
-      if constexpr (NKS == 8) v += dpp<DPP_HALF_MIRROR>(v);
-      pre[gt] = v;
-    }
-    float ig, fg, gg, og;
-    if constexpr (NKS >= 4) {
-      // lane ks (< 4): activation of gate ks (i, f, g, o = sig, sig, tanh, sig), branch-free
-      const float p01 = (ga & 1) ? pre[1] : pre[0];
-      const float p23 = (ga & 1) ? pre[3] : pre[2];
-      const float pg = ((ga & 2) ? p23 : p01) + g0;
-      const float k = ga == 2 ? 2.f : 1.f;
-      const float act = fmaf(k, sigm_fast(k * pg), ga == 2 ? -1.f : 0.f);
-      ig = act;
-      fg = dpp<DPP_BCAST1>(act);
-      gg = dpp<DPP_BCAST2>(act);
-      og = dpp<DPP_BCAST3>(act);
-    } else {
-      // lane 0: i (sig) and g (tanh); lane 1: f (sig) and o (sig)
-      const float pa = (ks ? pre[1] : pre[0]) + g0;
-      const float pb = (ks ? pre[3] : pre[2]) + g1;
-      const float a0 = sigm_fast(pa);
-      const float kb = ks ? 1.f : 2.f;
-      const float a1 = fmaf(kb, sigm_fast(kb * pb), ks ? 0.f : -1.f);
-      ig = a0;
-      gg = a1;
-      fg = dpp<DPP_BCAST1>(a0);  // quad_perm [1,1,1,1]: lane 0 of the pair reads lane 1
-      og = dpp<DPP_BCAST1>(a1);
-      if constexpr (true) {      // pairs (2,3) of a quad take lane 3
-        const float fg3 = dpp<DPP_BCAST3>(a0), og3 = dpp<DPP_BCAST3>(a1);
-        const bool hi = (tid & 2) != 0;
-        fg = hi ? fg3 : fg;
-        og = hi ? og3 : og;
-      }
-    }
+    unit_matvec<KW, NKS, true>(hist[(t + 2 * CH - 1) % (2 * CH)] + ks * KW, w, pre);
+    float pa, pb = 0.f, ig, fg, gg, og;
+    gate_preacts<NKS>(pre, ga, g0, g1, pa, pb);
+    gates_to_lane0<NKS>(pa, pb, ga, ig, fg, gg, og);
     if (ks == 0) {
       cstate = fg * cstate + ig * gg;
       hist[t % (2 * CH)][u] = og * tanh_fast(cstate);
@@ -170,7 +265,12 @@ __global__ __launch_bounds__(NKS * H) void lstm_recurrent_kernel(
       }
     }
   };
-
+  // gate inputs prefetched two steps ahead (named registers, loop unrolled by two)
+  auto load_g = [&](int t, float& g0, float& g1) { load_gate_inputs<H, NKS == 2>(gp, gx_t, T, t, ga, g0, g1); };
+  float ga0 = 0.f, ga1 = 0.f, gb0 = 0.f, gb1 = 0.f;
+  load_g(0, ga0, ga1);
+  load_g(1, gb0, gb1);
+  __syncthreads();
   for (int t = 0; t < T; t += 2) {
     step(t, ga0, ga1);
     load_g(t + 2, ga0, ga1);
@@ -206,6 +306,7 @@ __global__ __launch_bounds__(64) void lstm_wave_kernel(
   const int u = lane / S, ks = lane % S;
   const int ws = blockIdx.y, seq = blockIdx.x;
   __shared__ __attribute__((aligned(16))) float hb[2][H];
+  // w[gate][j]: W_hh[ws][gate*H + u][ks*KW + j], packed in pairs
   f32x2l w[4][KW / 2];
 #pragma unroll
   for (int gt = 0; gt < 4; ++gt) {
@@ -221,69 +322,17 @@ __global__ __launch_bounds__(64) void lstm_wave_kernel(
   float* op = out + ws * o_ws + seq * o_seq + u;
   // taped forward: the cell states c_t too, [ws][seq][T][H] (the backward's cell scan input)
   float* cq = cout ? cout + ((int64_t)ws * gridDim.x + seq) * (int64_t)T * H + u : nullptr;
-  auto load_g = [&](int t, float& g0, float& g1) {
-    const float* q = gp + (int64_t)min(t, T - 1) * gx_t;
-    g0 = q[ks * H];
-    if constexpr (S == 2) g1 = q[(ks + 2) * H];
-  };
-  float ga0 = 0.f, ga1 = 0.f, gb0 = 0.f, gb1 = 0.f;
-  load_g(0, ga0, ga1);
-  load_g(1, gb0, gb1);
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 
   auto step = [&](int t, float g0, float g1) {
-    const float* hp = hb[(t + 1) & 1] + ks * KW;  // h(t-1)
-    f32x4 hv[KW / 4];
-#pragma unroll
-    for (int j = 0; j < KW / 4; ++j) hv[j] = reinterpret_cast<const f32x4*>(hp)[j];
-    f32x2l acc[4][2] = {};
-#pragma unroll
-    for (int j = 0; j < KW / 4; ++j) {
-      const f32x2l h01 = {hv[j][0], hv[j][1]}, h23 = {hv[j][2], hv[j][3]};
-#pragma unroll
-      for (int gt = 0; gt < 4; ++gt) {
-        acc[gt][j & 1] = __builtin_elementwise_fma(w[gt][2 * j], h01, acc[gt][j & 1]);
-        acc[gt][j & 1] = __builtin_elementwise_fma(w[gt][2 * j + 1], h23, acc[gt][j & 1]);
-      }
+    float part[4];
+    unit_matvec<KW, S, false>(hb[(t + 1) & 1] + ks * KW, w, part);  // h(t-1)
+    float pa, pb = 0.f, ig, fg, gg, og;
+    gate_preacts<S>(part, ks, g0, g1, pa, pb);
+    if (pp) {
+      pp[(int64_t)t * gx_t + ks * H] = pa;
+      if constexpr (S == 2) pp[(int64_t)t * gx_t + (ks + 2) * H] = pb;
     }
-    float pre[4];
-#pragma unroll
-    for (int gt = 0; gt < 4; ++gt) {
-      const f32x2l a2 = acc[gt][0] + acc[gt][1];
-      float v = a2[0] + a2[1];
-      v += dpp<DPP_XOR1>(v);
-      if constexpr (S == 4) v += dpp<DPP_XOR2>(v);
-      pre[gt] = v;
-    }
-    float ig, fg, gg, og;
-    if constexpr (S == 4) {
-      const float p01 = (ks & 1) ? pre[1] : pre[0];
-      const float p23 = (ks & 1) ? pre[3] : pre[2];
-      const float pg = ((ks & 2) ? p23 : p01) + g0;
-      if (pp) pp[(int64_t)t * gx_t + ks * H] = pg;
-      const float k = ks == 2 ? 2.f : 1.f;
-      const float act = fmaf(k, sigm_fast(k * pg), ks == 2 ? -1.f : 0.f);
-      ig = act;
-      fg = dpp<DPP_BCAST1>(act);
-      gg = dpp<DPP_BCAST2>(act);
-      og = dpp<DPP_BCAST3>(act);
-    } else {
-      // lane 0: i (sig) and g (tanh); lane 1: f (sig) and o (sig)
-      const float pa = (ks ? pre[1] : pre[0]) + g0;
-      const float pb = (ks ? pre[3] : pre[2]) + g1;
-      if (pp) {
-        pp[(int64_t)t * gx_t + ks * H] = pa;
-        pp[(int64_t)t * gx_t + (ks + 2) * H] = pb;
-      }
-      const float a0 = sigm_fast(pa);
-      const float kb = ks ? 1.f : 2.f;
-      const float a1 = fmaf(kb, sigm_fast(kb * pb), ks ? 0.f : -1.f);
-      ig = a0;
-      gg = a1;
-      // lane 0 of each pair reads lane 1: quad_perm [1,1,3,3]
-      fg = dpp<0xF5>(a0);
-      og = dpp<0xF5>(a1);
-    }
+    gates_to_lane0<S>(pa, pb, ks, ig, fg, gg, og);
     if (ks == 0) {
       cstate = fg * cstate + ig * gg;
       const float hn = og * tanh_fast(cstate);
@@ -295,7 +344,11 @@ __global__ __launch_bounds__(64) void lstm_wave_kernel(
     // the wait + clobber keep the compiler from moving the next step's reads above the write
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   };
-
+  auto load_g = [&](int t, float& g0, float& g1) { load_gate_inputs<H, S == 2>(gp, gx_t, T, t, ks, g0, g1); };
+  float ga0 = 0.f, ga1 = 0.f, gb0 = 0.f, gb1 = 0.f;
+  load_g(0, ga0, ga1);
+  load_g(1, gb0, gb1);
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   for (int t = 0; t < T; t += 2) {
     step(t, ga0, ga1);
     load_g(t + 2, ga0, ga1);
@@ -339,64 +392,29 @@ __global__ __launch_bounds__(NKS * H) void lstm_bwd_kernel(
   const float* dp = dh + ws * d_ws + seq * d_seq + u;
   float* cp = cbuf + ((int64_t)ws * gridDim.x + seq) * (int64_t)T * H + u;
   float* gp = dg + ws * g_ws + seq * g_seq + u;
-  auto acts = [&](int t, float& ig, float& fg, float& gg, float& og) {
-    const float* q = pp + (int64_t)t * p_t;
-    ig = sigm_fast(q[0]);
-    fg = sigm_fast(q[H]);
-    gg = fmaf(2.f, sigm_fast(2.f * q[2 * H]), -1.f);
-    og = sigm_fast(q[3 * H]);
-  };
-  if (ks == 0) {
-    float c = 0.f;
-#pragma unroll 4
-    for (int t = 0; t < T; ++t) {
-      float ig, fg, gg, og;
-      acts(t, ig, fg, gg, og);
-      c = fg * c + ig * gg;
-      cp[(int64_t)t * H] = c;
-    }
-  }
+  if (ks == 0) cell_scan<H>(pp, p_t, T, cp);
   // phase 1 wrote cbuf from lanes ks == 0 and phase 2 reads it from the same lanes: no barrier.
   // Phase 2 keeps every global load off the serial chain: step t-1's operands (gate
   // pre-activations, c_{t-1}, c_{t-2}, dh) are loaded right after step t's gate gradients, so
   // they are in flight during the barrier and the W_hh^T reduction.
   float dc = 0.f, dhr = 0.f;
-  float q0 = 0.f, q1 = 0.f, q2 = 0.f, q3 = 0.f, cc = 0.f, cpv = 0.f, dhin = 0.f;
-  auto fetch = [&](int t) {
-    const float* q = pp + (int64_t)t * p_t;
-    q0 = q[0];
-    q1 = q[H];
-    q2 = q[2 * H];
-    q3 = q[3 * H];
-    cc = cp[(int64_t)t * H];
-    cpv = t > 0 ? cp[(int64_t)(t - 1) * H] : 0.f;
-    dhin = dp[(int64_t)t * d_t];
-  };
-  if (ks == 0) fetch(T - 1);
+  BwdOp o{};
+  if (ks == 0) fetch_op<H>(pp, p_t, cp, dp, d_t, T - 1, o);
   for (int t = T - 1; t >= 0; --t) {
     const int buf = t & 1;
     if (ks == 0) {
-      const float ig = sigm_fast(q0), fg = sigm_fast(q1);
-      const float gg = fmaf(2.f, sigm_fast(2.f * q2), -1.f), og = sigm_fast(q3);
-      const float ct = cc, cprev = cpv;
-      const float tc = tanh_fast(ct);
-      const float dht = dhin + dhr;
-      dc = fmaf(dht * og, 1.f - tc * tc, dc);
-      const float a_i = dc * gg * ig * (1.f - ig);
-      const float a_f = dc * cprev * fg * (1.f - fg);
-      const float a_g = dc * ig * (1.f - gg * gg);
-      const float a_o = dht * tc * og * (1.f - og);
-      dc *= fg;
+      float a_i, a_f, a_g, a_o;
+      gate_grads(o, dhr, dc, a_i, a_f, a_g, a_o);
       das[buf][u] = a_i;
       das[buf][H + u] = a_f;
       das[buf][2 * H + u] = a_g;
       das[buf][3 * H + u] = a_o;
-      float* o = gp + (int64_t)t * g_t;
-      o[0] = a_i;
-      o[H] = a_f;
-      o[2 * H] = a_g;
-      o[3 * H] = a_o;
-      if (t > 0) fetch(t - 1);
+      float* go = gp + (int64_t)t * g_t;
+      go[0] = a_i;
+      go[H] = a_f;
+      go[2 * H] = a_g;
+      go[3 * H] = a_o;
+      if (t > 0) fetch_op<H>(pp, p_t, cp, dp, d_t, t - 1, o);
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // LDS-only barrier (loads stay in flight)
     __builtin_amdgcn_s_barrier();
@@ -410,12 +428,7 @@ __global__ __launch_bounds__(NKS * H) void lstm_bwd_kernel(
       s0 = fmaf(wc[4 * j + 2], v[2], s0);
       s1 = fmaf(wc[4 * j + 3], v[3], s1);
     }
-    float s = s0 + s1;
-    // NKS = 8 slices of a unit are 8 adjacent lanes: DPP xor1, xor2, half-row mirror
-    s += dpp<DPP_XOR1>(s);
-    s += dpp<DPP_XOR2>(s);
-    s += dpp<DPP_HALF_MIRROR>(s);
-    dhr = s;
+    dhr = group_sum<NKS>(s0 + s1);  // the 8 slices of a unit: 8 adjacent lanes
   }
 }
 
@@ -457,44 +470,15 @@ __global__ __launch_bounds__(64) void lstm_bwd_wave_kernel(
   // phase 1: the cell scan, by every lane of the unit (identical values to the same address;
   // each lane reads back only what it wrote itself) — unless the taped forward stored the cell
   // states already (c_ready: lstm_wave_kernel's cout; the serial scan is ~half of this kernel)
-  if (!c_ready) {
-    float c = 0.f;
-#pragma unroll 4
-    for (int t = 0; t < T; ++t) {
-      const float* q = pp + (int64_t)t * p_t;
-      const float ig = sigm_fast(q[0]), fg = sigm_fast(q[H]);
-      const float gg = fmaf(2.f, sigm_fast(2.f * q[2 * H]), -1.f);
-      c = fg * c + ig * gg;
-      cp[(int64_t)t * H] = c;
-    }
-  }
-  struct Op {
-    float q0, q1, q2, q3, cc, cpv, dhin;
-  };
-  auto fetch = [&](int t, Op& o) {
-    if (t < 0) return;
-    const float* q = pp + (int64_t)t * p_t;
-    o.q0 = q[0];
-    o.q1 = q[H];
-    o.q2 = q[2 * H];
-    o.q3 = q[3 * H];
-    o.cc = cp[(int64_t)t * H];
-    o.cpv = t > 0 ? cp[(int64_t)(t - 1) * H] : 0.f;
-    o.dhin = dp[(int64_t)t * d_t];
+  if (!c_ready) cell_scan<H>(pp, p_t, T, cp);
+  auto fetch = [&](int t, BwdOp& o) {
+    if (t >= 0) fetch_op<H>(pp, p_t, cp, dp, d_t, t, o);
   };
   float dc = 0.f, dhr = 0.f;
-  auto step = [&](int t, const Op& o) {
+  auto step = [&](int t, const BwdOp& o) {
     const int buf = t & 1;
-    const float ig = sigm_fast(o.q0), fg = sigm_fast(o.q1);
-    const float gg = fmaf(2.f, sigm_fast(2.f * o.q2), -1.f), og = sigm_fast(o.q3);
-    const float tc = tanh_fast(o.cc);
-    const float dht = o.dhin + dhr;
-    dc = fmaf(dht * og, 1.f - tc * tc, dc);
-    const float a_i = dc * gg * ig * (1.f - ig);
-    const float a_f = dc * o.cpv * fg * (1.f - fg);
-    const float a_g = dc * ig * (1.f - gg * gg);
-    const float a_o = dht * tc * og * (1.f - og);
-    dc *= fg;
+    float a_i, a_f, a_g, a_o;
+    gate_grads(o, dhr, dc, a_i, a_f, a_g, a_o);
     float* go = gp + (int64_t)t * g_t;
     if constexpr (S == 2) {  // lane 0 of the unit: gates i, f; lane 1: g, o
       const float v0 = ks ? a_g : a_i, v1 = ks ? a_o : a_f;
@@ -531,12 +515,9 @@ __global__ __launch_bounds__(64) void lstm_bwd_wave_kernel(
       }
     }
     const f32x2l a = a0 + a1;
-    float s = a[0] + a[1];
-    s += dpp<DPP_XOR1>(s);
-    if constexpr (S == 4) s += dpp<DPP_XOR2>(s);
-    dhr = s;
+    dhr = group_sum<S>(a[0] + a[1]);
   };
-  Op o0{}, o1{}, o2{}, o3{};
+  BwdOp o0{}, o1{}, o2{}, o3{};
   fetch(T - 1, o0);
   fetch(T - 2, o1);
   fetch(T - 3, o2);
@@ -584,7 +565,7 @@ __global__ __launch_bounds__(4 * H) void lstm_cell_kernel(const float* __restric
 #pragma unroll 8
   for (int j = 0; j < H; ++j) a = fmaf(w[j], hs[j], a);
   const int gate = g / H;
-  act[g] = gate == 2 ? fmaf(2.f, sigm_fast(2.f * a), -1.f) : sigm_fast(a);
+  act[g] = gate == 2 ? tanh_gate(a) : sigm_fast(a);
   __syncthreads();
   if (g < H) {
     const float cn = act[H + g] * cp[g] + act[g] * act[2 * H + g];
@@ -602,13 +583,41 @@ extern "C" int clskd_lstm_pre_capable(int32_t H) {
   return H == 32 && knob(KNOB_LSTM_NKS32) == 1 && knob(KNOB_LSTM_PRE) != 0 ? 1 : 0;
 }
 
+// ---- host side: one validation and one hidden-size dispatch for the four entries ----
+// (aligned16: the pointer the kernel reads as float4s, or null for none)
+static int check_entry(const char* name, bool pointers, int nws, int nseq, int T,
+                       const void* aligned16) {
+  CLSKD_CHECK_ARG(pointers, "%s: null pointer", name);
+  CLSKD_CHECK_SHAPE(nws >= 1 && nseq >= 1 && T >= 1, "%s: empty shape", name);
+  CLSKD_CHECK_ARG(((uintptr_t)aligned16 & 15) == 0, "%s: whh must be 16-byte aligned", name);
+  return CLSKD_OK;
+}
+
+template <int V>
+struct Hidden {
+  static constexpr int value = V;
+};
+// launch(Hidden<H>{}) for a built hidden size, then the launch check
+template <class Launch>
+static int for_hidden_size(const char* name, const char* kernel, int H, Launch&& launch) {
+  switch (H) {
+    case 16: launch(Hidden<16>{}); break;
+    case 32: launch(Hidden<32>{}); break;
+    case 64: launch(Hidden<64>{}); break;
+    case 128: launch(Hidden<128>{}); break;
+    default:
+      set_error("%s: hidden size %d not built (16, 32, 64, 128)", name, H);
+      return CLSKD_E_SHAPE;
+  }
+  CLSKD_LAUNCH_CHECK(kernel);
+  return CLSKD_OK;
+}
+
 extern "C" int clskd_lstm_recurrent(const float* gx, int64_t gx_ws, int64_t gx_seq, int64_t gx_t,
                                     const float* whh, int32_t nws, int32_t nseq, int32_t T,
                                     int32_t H, float* out, int64_t o_ws, int64_t o_seq,
                                     int64_t o_t, void* stream) {
-  CLSKD_CHECK_ARG(gx && whh && out, "lstm: null pointer");
-  CLSKD_CHECK_SHAPE(nws >= 1 && nseq >= 1 && T >= 1, "lstm: empty shape");
-  CLSKD_CHECK_ARG(((uintptr_t)whh & 15) == 0, "lstm: whh must be 16-byte aligned");
+  if (const int rc = check_entry("lstm", gx && whh && out, nws, nseq, T, whh)) return rc;
   if (skip_kernel(SKIP_LSTM)) return CLSKD_OK;
   dim3 grid(nseq, nws);
   hipStream_t st = as_stream(stream);
@@ -633,11 +642,9 @@ extern "C" int clskd_lstm_recurrent(const float* gx, int64_t gx_ws, int64_t gx_s
 #define LSTM_LAUNCH(H_, NKS_) \
   hipLaunchKernelGGL((lstm_recurrent_kernel<H_, NKS_>), grid, dim3(NKS_ * H_), 0, st, gx, gx_ws, \
                      gx_seq, gx_t, whh, T, out, o_ws, o_seq, o_t, prio)
-  switch (H) {
-    case 16:
-      LSTM_LAUNCH(16, 4);
-      break;
-    case 32:
+  return for_hidden_size("lstm", "lstm_recurrent", H, [&](auto h) {
+    constexpr int H_ = decltype(h)::value;
+    if constexpr (H_ == 32) {
 #ifdef CLSKD_EXPERIMENTS
       if (const int td = knob(KNOB_LSTM32_TDIV)) T = max(1, T / max(1, td));  // timing only
 #endif
@@ -646,11 +653,7 @@ extern "C" int clskd_lstm_recurrent(const float* gx, int64_t gx_ws, int64_t gx_s
       else if (nks32 == 8) LSTM_LAUNCH(32, 8);
       else hipLaunchKernelGGL(lstm_wave_kernel<32>, grid, dim3(64), 0, st, gx, gx_ws, gx_seq, gx_t,
                               whh, T, out, o_ws, o_seq, o_t, prio, (float*)nullptr);
-      break;
-    case 64:
-      LSTM_LAUNCH(64, 4);
-      break;
-    case 128:
+    } else if constexpr (H_ == 128) {
 #ifdef CLSKD_EXPERIMENTS
       // timing experiment only (wrong results): CLSKD_LSTM128_TDIV = d runs T / d steps
       if (const int td = knob(KNOB_LSTM128_TDIV)) T = max(1, T / max(1, td));
@@ -658,23 +661,18 @@ extern "C" int clskd_lstm_recurrent(const float* gx, int64_t gx_ws, int64_t gx_s
       if (nks128 == 8) LSTM_LAUNCH(128, 8);
       else if (nks128 == 4) LSTM_LAUNCH(128, 4);
       else LSTM_LAUNCH(128, 2);
-      break;
-    default:
-      set_error("lstm: hidden size %d not built (16, 32, 64, 128)", H);
-      return CLSKD_E_SHAPE;
-  }
+    } else {
+      LSTM_LAUNCH(H_, 4);
+    }
+  });
 #undef LSTM_LAUNCH
-  CLSKD_LAUNCH_CHECK("lstm_recurrent");
-  return CLSKD_OK;
 }
 
 extern "C" int clskd_lstm_recurrent_pre(float* gx, int64_t gx_ws, int64_t gx_seq, int64_t gx_t,
                                         const float* whh, int32_t nws, int32_t nseq, int32_t T,
                                         int32_t H, float* out, int64_t o_ws, int64_t o_seq,
                                         int64_t o_t, float* cbuf, void* stream) {
-  CLSKD_CHECK_ARG(gx && whh && out, "lstm_pre: null pointer");
-  CLSKD_CHECK_SHAPE(nws >= 1 && nseq >= 1 && T >= 1, "lstm_pre: empty shape");
-  CLSKD_CHECK_ARG(((uintptr_t)whh & 15) == 0, "lstm_pre: whh must be 16-byte aligned");
+  if (const int rc = check_entry("lstm_pre", gx && whh && out, nws, nseq, T, whh)) return rc;
   CLSKD_CHECK_SHAPE(clskd_lstm_pre_capable(H), "lstm_pre: H=%d runs on a kernel without the "
                     "pre-activation output (clskd_lstm_pre_capable)", H);
   if (skip_kernel(SKIP_LSTM_PRE)) return CLSKD_OK;
@@ -690,61 +688,39 @@ extern "C" int clskd_lstm_bwd(const float* pre, int64_t p_ws, int64_t p_seq, int
                               const float* whh, int32_t nws, int32_t nseq, int32_t T, int32_t H,
                               float* cbuf, int32_t c_ready, float* dgates, int64_t g_ws,
                               int64_t g_seq, int64_t g_t, void* stream) {
-  CLSKD_CHECK_ARG(pre && dh && whh && cbuf && dgates, "lstm_bwd: null pointer");
-  CLSKD_CHECK_SHAPE(nws >= 1 && nseq >= 1 && T >= 1, "lstm_bwd: empty shape");
+  if (const int rc = check_entry("lstm_bwd", pre && dh && whh && cbuf && dgates, nws, nseq, T, nullptr))
+    return rc;
   if (skip_kernel(SKIP_LSTM_BWD)) return CLSKD_OK;
   dim3 grid(nseq, nws);
   hipStream_t st = as_stream(stream);
-#define LSTM_BWD(H_, NKS_)                                                                     \
-  hipLaunchKernelGGL((lstm_bwd_kernel<H_, NKS_>), grid, dim3(NKS_ * H_), 0, st, pre, p_ws, p_seq, \
-                     p_t, dh, d_ws, d_seq, d_t, whh, T, cbuf, dgates, g_ws, g_seq, g_t)
   // H = 16 / 32: the single-wave kernel unless CLSKD_LSTM_BWD_WAVE=0 (A/B)
   const bool wave = knob(KNOB_LSTM_BWD_WAVE) != 0;
-  if (wave && (H == 16 || H == 32)) {
-    const bool pin = knob(KNOB_LSTM_BWD_PIN) != 0;
-#define LSTM_BWD_WAVE(H_, PIN_)                                                                   \
-  hipLaunchKernelGGL((lstm_bwd_wave_kernel<H_, PIN_>), grid, dim3(64), 0, st, pre, p_ws, p_seq,   \
-                     p_t, dh, d_ws, d_seq, d_t, whh, T, cbuf, dgates, g_ws, g_seq, g_t, c_ready)
-    if (H == 16) {
-      if (pin) LSTM_BWD_WAVE(16, true); else LSTM_BWD_WAVE(16, false);
-    } else {
-      if (pin) LSTM_BWD_WAVE(32, true); else LSTM_BWD_WAVE(32, false);
+  const bool pin = knob(KNOB_LSTM_BWD_PIN) != 0;
+#define LSTM_BWD_ARGS pre, p_ws, p_seq, p_t, dh, d_ws, d_seq, d_t, whh, T, cbuf, dgates, g_ws, g_seq, g_t
+  return for_hidden_size("lstm_bwd", "lstm_bwd", H, [&](auto h) {
+    constexpr int H_ = decltype(h)::value;
+    if constexpr (H_ <= 32) {
+      if (wave) {
+        if (pin) hipLaunchKernelGGL((lstm_bwd_wave_kernel<H_, true>), grid, dim3(64), 0, st, LSTM_BWD_ARGS, c_ready);
+        else hipLaunchKernelGGL((lstm_bwd_wave_kernel<H_, false>), grid, dim3(64), 0, st, LSTM_BWD_ARGS, c_ready);
+        return;
+      }
     }
-#undef LSTM_BWD_WAVE
-    CLSKD_LAUNCH_CHECK("lstm_bwd");
-    return CLSKD_OK;
-  }
-  switch (H) {
-    case 16: LSTM_BWD(16, 8); break;
-    case 32: LSTM_BWD(32, 8); break;
-    case 64: LSTM_BWD(64, 8); break;
-    case 128: LSTM_BWD(128, 8); break;
-    default:
-      set_error("lstm_bwd: hidden size %d not built (16, 32, 64, 128)", H);
-      return CLSKD_E_SHAPE;
-  }
-#undef LSTM_BWD
-  CLSKD_LAUNCH_CHECK("lstm_bwd");
-  return CLSKD_OK;
+    hipLaunchKernelGGL((lstm_bwd_kernel<H_, 8>), grid, dim3(8 * H_), 0, st, LSTM_BWD_ARGS);
+  });
+#undef LSTM_BWD_ARGS
 }
 
 extern "C" int clskd_lstm_cell(const float* gx, int64_t gx_ws, int64_t gx_seq, const float* whh,
                                int32_t nws, int32_t nseq, int32_t H, float* h, float* c,
                                int64_t s_ws, int64_t s_seq, float* out, int64_t o_ws, int64_t o_seq,
                                void* stream) {
-  CLSKD_CHECK_ARG(gx && whh && h && c && out, "lstm_cell: null pointer");
-  CLSKD_CHECK_SHAPE(nws >= 1 && nseq >= 1, "lstm_cell: empty shape");
+  if (const int rc = check_entry("lstm_cell", gx && whh && h && c && out, nws, nseq, 1, nullptr)) return rc;
   dim3 grid(nseq, nws);
   hipStream_t st = as_stream(stream);
-  switch (H) {
-    case 16: hipLaunchKernelGGL(lstm_cell_kernel<16>, grid, dim3(64), 0, st, gx, gx_ws, gx_seq, whh, h, c, s_ws, s_seq, out, o_ws, o_seq); break;
-    case 32: hipLaunchKernelGGL(lstm_cell_kernel<32>, grid, dim3(128), 0, st, gx, gx_ws, gx_seq, whh, h, c, s_ws, s_seq, out, o_ws, o_seq); break;
-    case 64: hipLaunchKernelGGL(lstm_cell_kernel<64>, grid, dim3(256), 0, st, gx, gx_ws, gx_seq, whh, h, c, s_ws, s_seq, out, o_ws, o_seq); break;
-    case 128: hipLaunchKernelGGL(lstm_cell_kernel<128>, grid, dim3(512), 0, st, gx, gx_ws, gx_seq, whh, h, c, s_ws, s_seq, out, o_ws, o_seq); break;
-    default:
-      set_error("lstm_cell: hidden size %d not built (16, 32, 64, 128)", H);
-      return CLSKD_E_SHAPE;
-  }
-  CLSKD_LAUNCH_CHECK("lstm_cell");
-  return CLSKD_OK;
+  return for_hidden_size("lstm_cell", "lstm_cell", H, [&](auto hh) {
+    constexpr int H_ = decltype(hh)::value;
+    hipLaunchKernelGGL(lstm_cell_kernel<H_>, grid, dim3(4 * H_), 0, st, gx, gx_ws, gx_seq, whh, h, c,
+                       s_ws, s_seq, out, o_ws, o_seq);
+  });
 }

@@ -49,7 +49,7 @@ __global__ __launch_bounds__(shop::NT) void stream_hop_kernel(const clskd_stream
   const int tid = threadIdx.x;
   const int t = a.t;
   float* st = a.state + (int64_t)b * a.state_stride;
-  const int H = a.H, D4 = a.D4, C6 = a.enc_cout[5], Ch = C6 / 2, G4 = 4 * H;
+  const int H = a.H, D4 = a.D4, C6 = a.enc_cout[5], Ch = C6 / 2;
 
   __shared__ __attribute__((aligned(16))) float xw[WIN];
   __shared__ __attribute__((aligned(16))) float spec[NBIN + 2];
@@ -137,64 +137,10 @@ __global__ __launch_bounds__(shop::NT) void stream_hop_kernel(const clskd_stream
     }
     // cur = encoder 5 output [D4][C6] of frame t
     // ---- complex LSTMs (DCCRN.py:178-199), (h, c) carried across hops
-    for (int li = 0; li < 2; ++li) {
-      const int K = li == 0 ? D4 * Ch : H;
-      float* xin = win;  // [2][K]
-      float* hs = st + a.off_h + li * 4 * H;  // [ws][half][H]
-      float* cs = st + a.off_c + li * 4 * H;
-      // gate q = (ws, half, g), W_hh row n = ws*4H + g
-      const bool gate = tid < 4 * G4;
-      const int lh = lg2(H), lg4 = lh + 2;  // G4 = 4H
-      const int q = gate ? tid : 0, ws = q >> (lg4 + 1), half = (q >> lg4) & 1, gg = q & (G4 - 1), n = ws * G4 + gg;
-      // gx[half][n] (n < 8H: both weight sets side by side); staged: the input halves (layer 0
-      // x[k = f*Ch + c] = enc5[f][half*Ch + c]; layer 1 the combine output), (h, c) and W_hh
-      // (rows padded to H + 4 floats: the gate loop's row-per-lane quad reads are conflict-free)
-      gemv(a.lstm_w[li], a.lstm_b[li], L(xin), K, 2, K / 4, 8 * H, L(&gx[0][0]), 8 * 64, L(red), L(zr), [&]() {
-        if (li == 0) {  // encoder 5's frame t -> its ring (behind the first weight loads)
-          float* er = st + a.off_enc[5] + (int64_t)ring(t, 2) * D4 * C6;
-          for (int q2 = tid; q2 < D4 * C6; q2 += NT) er[q2] = cur[q2];
-        }
-        for (int q2 = tid; q2 < (H / 4) * 2 * G4; q2 += NT) {
-          const int j4 = q2 >> (lg4 + 1), r = q2 & (2 * G4 - 1);
-          *reinterpret_cast<f32x4*>(&whh[r * (H + 4) + j4 * 4]) = ldg4(a.lstm_whh[li] + (size_t)q2 * 4);
-        }
-        for (int q2 = tid; q2 < 2 * K; q2 += NT) {
-          const int lk = lg2(K), lch = lg2(Ch);
-          const int half2 = q2 >> lk, k = q2 & (K - 1);
-          xin[q2] = li == 0 ? cur[(k >> lch) * C6 + half2 * Ch + (k & (Ch - 1))] : rin[half2][k];
-        }
-        for (int q2 = tid; q2 < 4 * H; q2 += NT) {
-          (&hv[0][0][0])[(q2 >> lh) * 64 + (q2 & (H - 1))] = hs[q2];
-          (&cv[0][0][0])[(q2 >> lh) * 64 + (q2 & (H - 1))] = cs[q2];
-        }
-      });
-      __syncthreads();
-      // gates as clskd_lstm_cell: a = gx + W_hh[ws][g] . h[ws][half]
-      if (gate) {
-        f32x2 s2 = f32x2{gx[half][n], 0.f};
-        for (int j4 = 0; j4 < H / 4; ++j4) fma4(s2, ld4(L(&whh[n * (H + 4) + j4 * 4])), ld4(L(&hv[ws][half][j4 * 4])));
-        const float s = s2.x + s2.y;
-        act[ws][half][gg] = (gg >> lh) == 2 ? fmaf(2.f, sigm(2.f * s), -1.f) : sigm(s);
-      }
-      __syncthreads();
-      for (int q2 = tid; q2 < 4 * H; q2 += NT) {
-        const int ws2 = q2 >> (lh + 1), half2 = (q2 >> lh) & 1, u = q2 & (H - 1);
-        const float* ac = act[ws2][half2];
-        const float cn = ac[H + u] * cv[ws2][half2][u] + ac[u] * ac[2 * H + u];
-        const float hn = ac[3 * H + u] * tanh_f(cn);
-        cs[q2] = cn;
-        hs[q2] = hn;
-        hv[ws2][half2][u] = hn;
-      }
-      __syncthreads();
-      // real = R(r) - I(i), imag = R(i) + I(r)  (tools_for_model.py:168-169)
-      for (int q2 = tid; q2 < 2 * H; q2 += NT) {
-        const int half2 = q2 >> lh, u = q2 & (H - 1);
-        rin[half2][u] = half2 == 0 ? hv[0][0][u] - hv[1][1][u] : hv[0][1][u] + hv[1][0][u];
-      }
-      __syncthreads();
-      HOP_MARK(8 + li);
-    }
+    lstm_hop(LstmLds{L(win), L(&gx[0][0]), L(&hv[0][0][0]), L(&cv[0][0][0]), L(&act[0][0][0]), L(whh),
+                     L(&rin[0][0]), L(red), L(zr), L(cur)},
+             64, st + a.off_enc[5] + (int64_t)ring(t, 2) * D4 * C6, a.lstm_w, a.lstm_b, a.lstm_whh,
+             st + a.off_h, st + a.off_c, H, D4, C6);
     // projection (NavieComplexLSTM r_trans / i_trans): dec_in[f][half*Ch + c], n = c*D4 + f
     float* pj = &act[0][0][0];  // [2][Ch*D4] (the gate scratch is free now)
     for (int half = 0; half < 2; ++half) {

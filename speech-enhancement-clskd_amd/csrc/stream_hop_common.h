@@ -28,12 +28,6 @@ __device__ __forceinline__ int ring(int f, int D) { return ((f % D) + D) % D; }
 // log2 of a power of two (every shape the layer helpers divide by is one: host-checked)
 __device__ __forceinline__ int lg2(int v) { return 31 - __builtin_clz(v); }
 
-__device__ __forceinline__ float sigm(float x) {
-  return __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(-x * 1.4426950408889634f));
-}
-__device__ __forceinline__ float tanh_f(float x) {
-  return 1.f - 2.f * __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(x * 2.8853900817779268f));
-}
 // The layer helpers below are out-of-line (one copy of each in the code object: the whole hop
 // inlined was 121 KB of straight-line code, refetched from L2 by the instruction cache every hop),
 // so their pointers carry explicit address spaces: LDS operands as `lds`, global ones cast to
@@ -328,6 +322,82 @@ __device__ __forceinline__ void gemv(const float* W, const float* bias, const ld
     float v = bias ? ldg(bias + q % N) : 0.f;
     for (int s2 = 0; s2 < S; ++s2) v += red[s2 * M + q];
     y[(q / N) * ys + q % N] = v;
+  }
+}
+
+
+// The two complex-LSTM layers of a hop (nn.LSTM gates i, f, g, o; the four evaluations R(r), I(i),
+// R(i), I(r) of a layer in one pass; gates as clskd_lstm_cell), (h, c) carried across hops in
+// hs / cs [layer][ws][half][H] (global).  Inlined: one call site per hop kernel.
+// LDS scratch, 16-byte aligned where read as quads: xin [2][K] the staged input halves (layer 0:
+// x[k = f*Ch + c] = enc5[f][half*Ch + c] with K = D4*Ch, layer 1: the combine output, K = H),
+// gx [2][8*64] (gate inputs, both weight sets side by side), hv / cv [2][2][64], act [2][2][4*64],
+// whh [2*4H][H + 4] (rows padded by 4 floats: the gate loop's row-per-lane quad reads are
+// conflict-free), red / zr as gemv.  cur: encoder 5's frame [D4][C6] (LDS); e5ring: the slot of
+// encoder 5's ring that receives it (written behind the first weight loads).  rin: the layer
+// output, [re | im] rows of rs floats — the next layer's input and the caller's projection
+// operand.  w / b / whh_g: the args' lstm_w / lstm_b / lstm_whh.  Block-uniform; ends on a barrier.
+struct LstmLds {
+  lds *xin, *gx, *hv, *cv, *act, *whh, *rin, *red;
+  const lds *zr, *cur;
+};
+__device__ __forceinline__ void lstm_hop(const LstmLds s, int rs, float* e5ring, const float* const* w,
+                                         const float* const* b, const float* const* whh_g, float* hs0,
+                                         float* cs0, int H, int D4, int C6) {
+  const int tid = threadIdx.x;
+  const int Ch = C6 / 2, G4 = 4 * H;
+  for (int li = 0; li < 2; ++li) {
+    const int K = li == 0 ? D4 * Ch : H;
+    float* hs = hs0 + li * 4 * H;  // [ws][half][H]
+    float* cs = cs0 + li * 4 * H;
+    // gate q = (ws, half, g), W_hh row n = ws*4H + g
+    const bool gate = tid < 4 * G4;
+    const int lh = lg2(H), lg4 = lh + 2;  // G4 = 4H
+    const int q = gate ? tid : 0, ws = q >> (lg4 + 1), half = (q >> lg4) & 1, gg = q & (G4 - 1), n = ws * G4 + gg;
+    gemv(w[li], b[li], s.xin, K, 2, K / 4, 8 * H, s.gx, 8 * 64, s.red, s.zr, [&]() {
+      if (li == 0)
+        for (int q2 = tid; q2 < D4 * C6; q2 += NT) e5ring[q2] = s.cur[q2];
+      for (int q2 = tid; q2 < (H / 4) * 2 * G4; q2 += NT) {
+        const int j4 = q2 >> (lg4 + 1), r = q2 & (2 * G4 - 1);
+        *(__attribute__((address_space(3))) f32x4*)&s.whh[r * (H + 4) + j4 * 4] = ldg4(whh_g[li] + (size_t)q2 * 4);
+      }
+      for (int q2 = tid; q2 < 2 * K; q2 += NT) {
+        const int lk = lg2(K), lch = lg2(Ch);
+        const int half2 = q2 >> lk, k = q2 & (K - 1);
+        s.xin[q2] = li == 0 ? s.cur[(k >> lch) * C6 + half2 * Ch + (k & (Ch - 1))] : s.rin[half2 * rs + k];
+      }
+      for (int q2 = tid; q2 < 4 * H; q2 += NT) {
+        s.hv[(q2 >> lh) * 64 + (q2 & (H - 1))] = hs[q2];
+        s.cv[(q2 >> lh) * 64 + (q2 & (H - 1))] = cs[q2];
+      }
+    });
+    __syncthreads();
+    // a = gx + W_hh[ws][g] . h[ws][half]
+    if (gate) {
+      f32x2 s2 = f32x2{s.gx[half * 8 * 64 + n], 0.f};
+      for (int j4 = 0; j4 < H / 4; ++j4)
+        fma4(s2, ld4(&s.whh[n * (H + 4) + j4 * 4]), ld4(&s.hv[(ws * 2 + half) * 64 + j4 * 4]));
+      const float a = s2.x + s2.y;
+      s.act[(ws * 2 + half) * 4 * 64 + gg] = (gg >> lh) == 2 ? tanh_gate(a) : sigm_fast(a);
+    }
+    __syncthreads();
+    for (int q2 = tid; q2 < 4 * H; q2 += NT) {
+      const int wh = q2 >> lh, u = q2 & (H - 1);
+      const lds* ac = s.act + wh * 4 * 64;
+      const float cn = ac[H + u] * s.cv[wh * 64 + u] + ac[u] * ac[2 * H + u];
+      const float hn = ac[3 * H + u] * tanh_fast(cn);
+      cs[q2] = cn;
+      hs[q2] = hn;
+      s.hv[wh * 64 + u] = hn;
+    }
+    __syncthreads();
+    // real = R(r) - I(i), imag = R(i) + I(r)  (tools_for_model.py:168-169)
+    for (int q2 = tid; q2 < 2 * H; q2 += NT) {
+      const int half2 = q2 >> lh, u = q2 & (H - 1);
+      s.rin[half2 * rs + u] = half2 == 0 ? s.hv[u] - s.hv[3 * 64 + u] : s.hv[64 + u] + s.hv[2 * 64 + u];
+    }
+    __syncthreads();
+    CMARK(8 + li);
   }
 }
 

@@ -174,11 +174,11 @@ def _x3_case(case):
     assert _rel(_np(got), _np(dwe[:, :len(taps) * Cin].reshape(N, len(taps), Cin))) < 2e-5
 
 
-@pytest.mark.parametrize("H,wave", [(16, 1), (32, 1), (32, 0), (128, 1)])
+@pytest.mark.parametrize("H,wave", [(16, 1), (16, 0), (32, 1), (32, 0), (64, 1), (128, 1)])
 def test_lstm_bwd_against_torch(H, wave):
     """BPTT kernel: gate gradients for given dh, pre-activations rebuilt from the h history.
     H = 16 / 32 run the single-wave kernel (wave 1, default; T = 57 ends mid register ring) or
-    the 4-wave one (CLSKD_LSTM_BWD_WAVE=0)."""
+    the multi-wave one (CLSKD_LSTM_BWD_WAVE=0), which H = 64 / 128 always run."""
     from clskd import _lib, ops
     prev = _lib.set_knob("CLSKD_LSTM_BWD_WAVE", wave)
     try:

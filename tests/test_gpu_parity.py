@@ -1231,32 +1231,27 @@ def test_conv_gemm8_against_torch(case, lp, engine, loop="phased"):
 
 
 @pytest.mark.parametrize("prio", [0, 1])
-@pytest.mark.parametrize("variant", ["1", "8", "h128"])
+@pytest.mark.parametrize("variant", ["1", "2", "4", "8", "h16", "h64", "h128"])
 def test_lstm_recurrence_against_torch(variant, prio):
     """Complex-LSTM recurrence (tools_for_model.py:159-174, nn.LSTM gates i, f, g, o, zero
     state) at the student's H = 32 — the single-wave kernel (CLSKD_LSTM_NKS32=1, default) and the
-    8-slice multi-wave kernel — and the teacher's H = 128, each with and without the issue
-    priority (CLSKD_LSTM_PRIO), vs a torch fp64 recurrence on the same gate inputs.  Tolerance
-    2e-5 (v_exp / v_rcp gate activations, fp32 state)."""
+    2-, 4- and 8-slice multi-wave kernels — at H = 16 and 64 and at the teacher's H = 128, each
+    with and without the issue priority (CLSKD_LSTM_PRIO), vs a torch fp64 recurrence on the same
+    gate inputs.  Tolerance 2e-5 (v_exp / v_rcp gate activations, fp32 state)."""
     from clskd import _lib
-    prev = _lib.set_knob("CLSKD_LSTM_NKS32", 1 if variant == "h128" else int(variant))
+    prev = _lib.set_knob("CLSKD_LSTM_NKS32", 1 if variant[0] == "h" else int(variant))
     prev_p = _lib.set_knob("CLSKD_LSTM_PRIO", prio)
     try:
-        _lstm_recurrence_check(128 if variant == "h128" else 32)
+        _lstm_recurrence_check(int(variant[1:]) if variant[0] == "h" else 32)
     finally:
         _lib.set_knob("CLSKD_LSTM_NKS32", prev)
         _lib.set_knob("CLSKD_LSTM_PRIO", prev_p)
 
 
-def _lstm_recurrence_check(H=32):
-    from clskd import ops
-    g = torch.Generator().manual_seed(3)
-    nws, nseq, T = 2, 5, 37
-    gx = torch.randn(nseq, T, nws * 4 * H, generator=g)
-    whh = torch.randn(nws, 4 * H, H, generator=g) * (0.2 * (32 / H) ** 0.5)
-    out = torch.empty(nws, nseq, T, H, device=DEV)
-    ops.lstm_recurrent(gx.to(DEV), 4 * H, T * nws * 4 * H, nws * 4 * H, whh.to(DEV), nws, nseq, T, H,
-                       out, nseq * T * H, T * H, H)
+def _lstm_ref(gx, whh, H):
+    """fp64 recurrence from zero state: gx [nseq][T][nws*4H], whh [nws][4H][H] -> h [nws][nseq][T][H]."""
+    nseq, T = gx.shape[:2]
+    nws = whh.shape[0]
     ref = torch.empty(nws, nseq, T, H, dtype=torch.float64)
     for ws in range(nws):
         W = whh[ws].double()
@@ -1268,7 +1263,42 @@ def _lstm_recurrence_check(H=32):
             c = torch.sigmoid(f) * c + torch.sigmoid(i) * torch.tanh(gg)
             h = torch.sigmoid(o) * torch.tanh(c)
             ref[ws, :, t] = h
+    return ref
+
+
+def _lstm_recurrence_check(H=32):
+    from clskd import ops
+    g = torch.Generator().manual_seed(3)
+    nws, nseq, T = 2, 5, 37
+    gx = torch.randn(nseq, T, nws * 4 * H, generator=g)
+    whh = torch.randn(nws, 4 * H, H, generator=g) * (0.2 * (32 / H) ** 0.5)
+    out = torch.empty(nws, nseq, T, H, device=DEV)
+    ops.lstm_recurrent(gx.to(DEV), 4 * H, T * nws * 4 * H, nws * 4 * H, whh.to(DEV), nws, nseq, T, H,
+                       out, nseq * T * H, T * H, H)
+    ref = _lstm_ref(gx, whh, H)
     np.testing.assert_allclose(out.double().cpu().numpy(), ref.numpy(), rtol=2e-5, atol=2e-5)
+
+
+@pytest.mark.parametrize("H", [16, 32, 64, 128])
+def test_lstm_cell_against_torch(H):
+    """clskd_lstm_cell (the per-layer streaming classes' recurrence step) stepped from zero state
+    with carried (h, c) vs the torch fp64 recurrence on the same gate inputs, 2e-5 as the offline
+    recurrence; the step's output and the carried h are the same bits."""
+    from clskd import ops
+    g = torch.Generator().manual_seed(5)
+    nws, nseq, T = 2, 3, 5
+    gx = torch.randn(nseq, T, nws * 4 * H, generator=g)
+    whh = torch.randn(nws, 4 * H, H, generator=g) * (0.2 * (32 / H) ** 0.5)
+    ref = _lstm_ref(gx, whh, H)
+    gxd, whhd = gx.to(DEV), whh.to(DEV)
+    h = torch.zeros(nws, nseq, H, device=DEV)
+    c = torch.zeros(nws, nseq, H, device=DEV)
+    for t in range(T):
+        out = torch.full((nws, nseq, H), float("nan"), device=DEV)
+        ops.lstm_cell(gxd[:, t].contiguous(), 4 * H, nws * 4 * H, whhd, nws, nseq, H, h, c, nseq * H, H,
+                      out, nseq * H, H)
+        assert torch.equal(h, out), t
+        np.testing.assert_allclose(out.double().cpu().numpy(), ref[:, :, t].numpy(), rtol=2e-5, atol=2e-5)
 
 
 def _sk_expected(ntiles, nk, grid, force=False):

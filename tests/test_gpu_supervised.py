@@ -134,6 +134,33 @@ def test_autograd_dropin_and_train_step(kind, mode):
     assert isinstance(a.configure_optimizers(), torch.optim.Adam)
 
 
+def test_second_backward_over_one_tape_repeats_lstm_gradients():
+    """With CLSKD_LSTM_PRE=0 the taped forward leaves only the gate inputs in the tape and the
+    backward rebuilds the pre-activations in place, once per tape: a second backward_into over
+    the same forward_with_tape result gives the LSTM parameter gradients of the first, bitwise."""
+    from clskd import _lib
+    from clskd.supervised import SupervisedTraining
+    x, y = S.seeded_batch(**E2E)
+    prev = _lib.set_knob("CLSKD_LSTM_PRE", 0)
+    try:
+        mod = SupervisedTraining(_dccrn(), "MSE")
+        out = mod.forward_with_tape(x.to(DEV), y.to(DEV))
+        grads = []
+        for _ in range(2):
+            g = {p: torch.full_like(p, 7.0) for p in mod.student.parameters()}
+            mod.backward_into(out, g)
+            grads.append(g)
+        torch.cuda.synchronize()
+    finally:
+        _lib.set_knob("CLSKD_LSTM_PRE", prev)
+    lstm = [(n, p) for n, p in mod.student.named_parameters()
+            if n.startswith("enhance.") and ("weight_ih" in n or "weight_hh" in n or "bias_ih" in n
+                                             or "bias_hh" in n)]
+    assert len(lstm) == 2 * 2 * 4  # two layers x (real, imag) x four tensors
+    for n, p in lstm:
+        assert torch.equal(grads[0][p], grads[1][p]), n
+
+
 def test_unsupported_modes_raise():
     import clskd
     from clskd import config as cfg
