@@ -335,6 +335,13 @@ int clskd_complex_combine_dt(const float* rr, const float* ii, const float* ir, 
  *                  imag at 257.., zero tail) and optionally mask_r/mask_i [B][T][257].
  *                  1 <= B <= 65535, T >= 1 (a block per utterance and 16 frames); the same
  *                  bounds hold for clskd_mask_e_bwd.
+ * clskd_mask_cr:   DCCRN masking_mode 'C' (mode CLSKD_MASK_C: est = spec * mask, complex) and 'R'
+ *                  (CLSKD_MASK_R: est_re = re * mask_re, est_im = im * mask_im), DCCRN.py:227-230,
+ *                  on the layouts of clskd_mask_e: the mask is read at time t+1 and bin f-1, the
+ *                  DC bin sees a zero mask, est columns >= 514 are written as zero, mask_r /
+ *                  mask_i [B][T][257] are optional (both or neither).  ldspec >= 514, 514 <=
+ *                  ldest <= 771, Tm >= T + 1, 1 <= B <= 65535, T >= 1; any other mode is refused.
+ *                  The same bounds hold for clskd_mask_cr_bwd.
  * clskd_ola:       ConviSTFT overlap-add (tools_for_model.py:95-107): frames [B][T][400] ->
  *                  wav[b][n] = (sum frames) / (sum window^2 + 1e-8), trimmed, clamp(-1,1)
  *                  (DCCRN.py:235-237) when clamp != 0.  window == NULL: the plain sum
@@ -351,6 +358,11 @@ int clskd_spec_bftc(const float* spec, int32_t B, int32_t T, int32_t ld, int32_t
 int clskd_mask_e(const float* spec, int32_t ldspec, const float* mask, int32_t Tm, int32_t B,
                  int32_t T, float* est, int32_t ldest, float* mask_r, float* mask_i,
                  void* stream);
+#define CLSKD_MASK_C 1
+#define CLSKD_MASK_R 2
+int clskd_mask_cr(int32_t mode, const float* spec, int32_t ldspec, const float* mask, int32_t Tm,
+                  int32_t B, int32_t T, float* est, int32_t ldest, float* mask_r, float* mask_i,
+                  void* stream);
 int clskd_mask_bdt(const float* spec, int32_t ldspec, const float* mask, int32_t Tm, int32_t B,
                    int32_t T, float* est, int32_t ldest, void* stream);
 int clskd_ola(const float* frames, const float* window, int32_t B, int32_t T, int32_t win,
@@ -694,6 +706,13 @@ int clskd_nearest_down_sum(const void* g, int32_t B, int32_t F, int32_t T, int32
  * Complex-LSTM combine backward (tools_for_model.py:168-169): dh[2][2B][n] from dreal/dimag. */
 int clskd_mask_e_bwd(const float* spec, int32_t ldspec, const float* mask, int32_t Tm, int32_t B,
                      int32_t T, const float* dest, int32_t ldest, float* dmask, void* stream);
+/* Masking modes 'C' / 'R' backward (mode as clskd_mask_cr): d est -> d mask, written in full as
+ * clskd_mask_e_bwd writes it (time 0 and times > T zero).  'C': dmr = g_re re + g_im im, dmi =
+ * g_im re - g_re im; 'R': dmr = g_re re, dmi = g_im im.  Both are linear in the mask, so `mask`
+ * (required, for one signature with 'E') is not read; there is no gradient to the spectrum. */
+int clskd_mask_cr_bwd(int32_t mode, const float* spec, int32_t ldspec, const float* mask,
+                      int32_t Tm, int32_t B, int32_t T, const float* dest, int32_t ldest,
+                      float* dmask, void* stream);
 int clskd_ola_bwd(const float* frames, const float* window, const float* dwav, int32_t B,
                   int32_t T, int32_t win, int32_t hop, int32_t out_len, int32_t trim,
                   int32_t clamp, float* dframes, void* stream);

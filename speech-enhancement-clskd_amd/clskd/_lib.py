@@ -240,6 +240,8 @@ SIGNATURES = {
     "clskd_split_planes": (_i32, [_p, _i64, _i32, _p, _p]),
     "clskd_pack_split3": (_i32, [_p, _i32, _i32, _i32, _i32, _i32, _p, _p]),
     "clskd_mask_e_bwd": (_i32, [_p, _i32, _p, _i32, _i32, _i32, _p, _i32, _p, _p]),
+    "clskd_mask_cr": (_i32, [_i32, _p, _i32, _p, _i32, _i32, _i32, _p, _i32, _p, _p, _p]),
+    "clskd_mask_cr_bwd": (_i32, [_i32, _p, _i32, _p, _i32, _i32, _i32, _p, _i32, _p, _p]),
     "clskd_ola_bwd": (_i32, [_p, _p, _p, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _p, _p]),
     "clskd_frame_pad_bwd": (_i32, [_p, _i32, _i32, _i32, _i32, _i32, _p, _i64, _i32, _p]),
     "clskd_stft_mag_loss_bwd": (_i32, [_p, _p, _i64, _i32, _i32, _f32, _p, _i32, _p]),

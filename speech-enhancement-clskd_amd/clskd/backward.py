@@ -351,13 +351,13 @@ def dccrn_backward(m, tape, enc, dec, dec_in, lstm_io, g, pg, acc_params=False, 
     # framing GEMMs below — only a student whose compute mode is 'f32x3' leaves the exact engine
     planes = getattr(m, "compute", "fp32") == "f32x3"
 
-    # ---------------- ConviSTFT + clamp + mask 'E' (DCCRN.py:207-237)
+    # ---------------- ConviSTFT + clamp + mask 'E' / 'C' / 'R' (DCCRN.py:207-237)
     dmask = None
     gest = g.get("est_spec")
     if gest is not None and g.get("wav") is None:  # a spectrum-only loss
         assert gest.shape[:2] == (B, T) and gest.shape[-1] >= 514 and gest.is_contiguous()
         dmask = _empty(dec[-1].shape, dev)
-        ops.mask_e_bwd(tape["spec"], dec[-1], T, gest, dmask)
+        ops.mask_bwd(m.masking_mode, tape["spec"], dec[-1], T, gest, dmask)
     elif g.get("wav") is not None:
         frames, window, out_len = tape["frames"], tape["window"], tape["out_len"]
         dframes = _empty((B, T, 400), dev)
@@ -379,7 +379,7 @@ def dccrn_backward(m, tape, enc, dec, dec_in, lstm_io, g, pg, acc_params=False, 
             ops.check(ops.lib().clskd_axpy_f32(ops.ptr(gest), ops.ptr(dest), dest.numel(), 1.0, 1,
                                                ops._stream()), "est_spec add")
         dmask = _empty(dec[-1].shape, dev)
-        ops.mask_e_bwd(tape["spec"], dec[-1], T, dest, dmask)
+        ops.mask_bwd(m.masking_mode, tape["spec"], dec[-1], T, dest, dmask)
 
     # ---------------- decoder (DCCRN.py:201-206), reverse
     F_in = [dec_in.shape[1] * (2 ** d) for d in range(nl)]  # input freq of decoder layer d
@@ -447,21 +447,32 @@ def dccrn_backward(m, tape, enc, dec, dec_in, lstm_io, g, pg, acc_params=False, 
             ops.conv([dseg], taps_b, B, F, T, Cs, wt, None, dst, OutMap(F * Tt * Cs, Tt * Cs, Cs),
                      out_offset=t0 * Cs, stride_f=2, accumulate=True)
 
-    # ---------------- LSTM projection + complex LSTMs (DCCRN.py:178-199), reverse
+    # ---------------- LSTM projection + (complex) LSTMs (DCCRN.py:178-199), reverse
     C6 = kn[-1]
-    Ch = C6 // 2
     D4 = dec_in.shape[1]
-    H = m.rnn_units // 2
-    last = m.enhance[m.hidden_layers - 1]
-    P = last.projection_dim
-    packs_last = m._lstm_w(m.hidden_layers - 1, "fp32")
-    ro, io = lstm_io[-1]
-    d_out = [_empty((B, T, H), dev), _empty((B, T, H), dev)]
-    for half in range(2):
+    # S input halves of Ch channels, each with its own projection out of a layer output of H units:
+    # the complex stack's (real, imag) with r_trans / i_trans, or the real LSTM's one with `tranform`
+    if m.use_clstm:
+        S, H = 2, m.rnn_units // 2
+        last = m.enhance[m.hidden_layers - 1]
+        lins = (last.r_trans, last.i_trans)
+        packs_last = m._lstm_w(m.hidden_layers - 1, "fp32")
+        weights = lambda li: m._lstm_w(li, "fp32")[:3]  # noqa: E731
+        lstms = [(mod.real_lstm, mod.imag_lstm) for mod in m.enhance]
+    else:
+        S, H = 1, m.rnn_units
+        lins = (m.tranform,)
+        packs_last = m._rlstm_w(1, "fp32")
+        weights = lambda li: m._rlstm_w(li, "fp32")[:3]  # noqa: E731
+        lstms = [(clstm.layer_view(m.enhance, li),) for li in range(2)]
+    Ch = C6 // S
+    P = Ch * D4
+    d_out = [_empty((B, T, H), dev) for _ in range(S)]
+    for half in range(S):
         wpp, bp = packs_last[3 + 2 * half], packs_last[4 + 2 * half]
-        lin = last.r_trans if half == 0 else last.i_trans
+        lin = lins[half]
         omap = OutMap(D4 * T * C6, 0, C6, 1, T * C6, D4)
-        src = (ro, io)[half]
+        src = lstm_io[-1][half]
         segs = [Seg(src, 0, SegGeom(H, T * H, 0, H, 1, T))]
         dw = _empty(wpp.shape, dev)
         db = _empty((P,), dev)
@@ -476,10 +487,8 @@ def dccrn_backward(m, tape, enc, dec, dec_in, lstm_io, g, pg, acc_params=False, 
         ops.conv([dseg], [(f, 0) for f in range(D4)], B, 1, T, H, wt, None, d_out[half],
                  OutMap(T * H, 0, H), mfma_only=True)
     in0 = [([seg_bftc(enc[-1], c0=half * Ch, C=Ch)], [(f, 0) for f in range(D4)])
-           for half in range(2)]
-    clstm.backward(d_out, tape, lambda li: m._lstm_w(li, "fp32")[:3],
-                   [(mod.real_lstm, mod.imag_lstm) for mod in m.enhance], in0, g["enc"][-1], m, pg,
-                   acc_params)
+           for half in range(S)]
+    clstm.backward(d_out, tape, weights, lstms, in0, g["enc"][-1], m, pg, acc_params)
 
     # ---------------- encoder (DCCRN.py:171-176), reverse
     for i in range(nl - 1, -1, -1):

@@ -64,8 +64,10 @@ def _norm_shapes(s, p, channels, use_cbn):
     s[p + "num_batches_tracked"] = ()
 
 
-def dccrn_param_shapes(rnn_units, kernel_num, rnn_layers=2, ksize=5, fft=fft_len, use_cbn=False):
-    """Ordered {state_dict key: shape} of the reference DCCRN (use_clstm=True; use_cbn as given)."""
+def dccrn_param_shapes(rnn_units, kernel_num, rnn_layers=2, ksize=5, fft=fft_len, use_cbn=False,
+                       use_clstm=True):
+    """Ordered {state_dict key: shape} of the reference DCCRN (use_cbn and use_clstm as given;
+    use_clstm=False: the two-layer nn.LSTM `enhance` and the Linear `tranform`, DCCRN.py:101-109)."""
     kn = [2] + list(kernel_num)
     s = OrderedDict()
     for i in range(len(kn) - 1):
@@ -79,7 +81,15 @@ def dccrn_param_shapes(rnn_units, kernel_num, rnn_layers=2, ksize=5, fft=fft_len
     hidden_dim = fft // (2 ** len(kn))
     feat = hidden_dim * kn[-1]
     enh = OrderedDict()  # registered after encoder/decoder ModuleLists (DCCRN.py:66-67 vs :88-99)
-    for li in range(rnn_layers):
+    if not use_clstm:
+        for li in range(2):  # num_layers=2 whatever rnn_layers says
+            for k, cols in (("weight_ih", feat if li == 0 else rnn_units), ("weight_hh", rnn_units)):
+                enh[f"enhance.{k}_l{li}"] = (4 * rnn_units, cols)
+            for k in ("bias_ih", "bias_hh"):
+                enh[f"enhance.{k}_l{li}"] = (4 * rnn_units,)
+        enh["tranform.weight"] = (feat, rnn_units)
+        enh["tranform.bias"] = (feat,)
+    for li in range(rnn_layers if use_clstm else 0):
         p = f"enhance.{li}."
         din = (feat if li == 0 else rnn_units) // 2
         h = rnn_units // 2

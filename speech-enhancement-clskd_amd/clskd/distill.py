@@ -27,7 +27,7 @@ import torch.nn as nn
 from . import config as cfg
 from . import _lib, ops
 from .framework import MultiResolutionSTFTLoss, SPKDLoss, build_review_kd
-from .model import DCCRN, refuse_cbn
+from .model import DCCRN, refuse_cbn, refuse_mask_mode, refuse_real_lstm
 
 
 _SIDE = {}
@@ -176,6 +176,10 @@ class KnowledgeDistillation(nn.Module):
         super().__init__()
         refuse_cbn(teacher, "KnowledgeDistillation")
         refuse_cbn(student, "KnowledgeDistillation")
+        refuse_mask_mode(teacher, "KnowledgeDistillation")
+        refuse_real_lstm(teacher, "KnowledgeDistillation")
+        refuse_mask_mode(student, "KnowledgeDistillation")
+        refuse_real_lstm(student, "KnowledgeDistillation")
         self.automatic_optimization = True
         self.teacher = teacher
         for p in self.teacher.parameters():
@@ -582,6 +586,10 @@ class SPKDDistillation(nn.Module):
         super().__init__()
         refuse_cbn(teacher, "SPKDDistillation")
         refuse_cbn(student, "SPKDDistillation")
+        refuse_mask_mode(teacher, "SPKDDistillation")
+        refuse_real_lstm(teacher, "SPKDDistillation")
+        refuse_mask_mode(student, "SPKDDistillation")
+        refuse_real_lstm(student, "SPKDDistillation")
         self.teacher = teacher
         for p in self.teacher.parameters():
             p.requires_grad = False

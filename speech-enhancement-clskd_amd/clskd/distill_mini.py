@@ -22,7 +22,7 @@ from .asteroid_backward import mini_backward
 from .backward import mrstft_backward
 from .distill import _validation_step
 from .framework import MultiResolutionSTFTLoss, SPKDLoss
-from .model import DCCRN, refuse_cbn
+from .model import DCCRN, refuse_cbn, refuse_mask_mode, refuse_real_lstm
 
 KD_KINDS = ("spkd", "mse", "stft")
 
@@ -47,6 +47,8 @@ class OutputDistillation(nn.Module):
                  spkd_loss=SPKDLoss, cfg=cfg):
         super().__init__()
         refuse_cbn(teacher, "OutputDistillation")
+        refuse_mask_mode(teacher, "OutputDistillation")
+        refuse_real_lstm(teacher, "OutputDistillation")
         if kd not in KD_KINDS:
             raise ValueError(f"kd must be one of {KD_KINDS}, got {kd!r}")
         if not isinstance(student, DCCRNet_mini):

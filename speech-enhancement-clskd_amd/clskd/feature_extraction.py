@@ -6,12 +6,14 @@ The reference registers forward hooks; ``clskd.DCCRN`` runs as one HIP executor,
 delivered through a tap sink instead (same lifetime semantics: ``remove_hook`` detaches it).
 """
 from .model import DCCRN as _DCCRNModel
+from .model import refuse_real_lstm
 
 
 class DCCRN:
     def __init__(self, model):
         if not isinstance(model, _DCCRNModel):
             raise TypeError("feature_extraction.DCCRN expects a clskd.DCCRN model")
+        refuse_real_lstm(model, "feature_extraction.DCCRN (its taps have a complex clstm pair)")
         self.model = model
         self.feature_maps = {"encoder": [], "decoder": [], "clstm": []}
         self._sink = self._collect

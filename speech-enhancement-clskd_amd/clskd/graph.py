@@ -23,7 +23,7 @@ import torch
 
 from . import ops
 from .distill import KnowledgeDistillation
-from .model import refuse_cbn
+from .model import refuse_cbn, refuse_mask_mode, refuse_real_lstm
 
 
 def _bn_buffers(kd):
@@ -44,6 +44,8 @@ class StepGraph:
                             "SPKDDistillation (C4) step")
         for m in (kd.teacher, kd.student):
             refuse_cbn(m, "a captured step graph")
+            refuse_mask_mode(m, "a captured step graph")
+            refuse_real_lstm(m, "a captured step graph")
         if not X.is_cuda:
             raise RuntimeError("StepGraph needs device-resident inputs")
         self.kd = kd

@@ -9,7 +9,12 @@ libclskd_hip.so on BFTC ([batch][freq][time][channel]) buffers, never through to
 Supported configuration = the one the reference trains and distils: masking_mode 'E',
 use_clstm=True, kernel_size 5, fft 512 / win 400 / hop 100, with either normalisation the
 reference offers: nn.BatchNorm2d (use_cbn=False) or ComplexBatchNorm (use_cbn=True, fp32
-activations; forward, taps, DCCRN.loss and SupervisedTraining).  Anything else raises.
+activations; forward, taps, DCCRN.loss and SupervisedTraining), and the rest of the DCCRN
+family: the reference's other two masks, masking_mode 'C' and 'R' (fp32 activations; forward,
+taps, DCCRN.loss, SupervisedTraining and the per-layer StreamingDCCRN), and its real two-layer
+LSTM bottleneck, use_clstm=False with rnn_units in REAL_LSTM_UNITS (fp32 activations; forward,
+DCCRN.loss and SupervisedTraining).  Mask 'C' runs on the real LSTM only: with use_clstm=True it
+stays refused, as before.  Anything else raises.
 """
 import os
 import weakref
@@ -207,6 +212,25 @@ def refuse_cbn(model, who):
         raise NotImplementedError(f"{who} does not support a DCCRN built with use_cbn=True")
 
 
+REAL_LSTM_UNITS = (16, 32, 64, 128)  # hidden sizes csrc/lstm.hip is built for
+
+
+def refuse_real_lstm(model, who):
+    """Consumers built around the complex-LSTM pair (its tap contract, its streaming state, the
+    fused hop kernel, the distillation steps) refuse a DCCRN(use_clstm=False)."""
+    if not getattr(model, "use_clstm", True):
+        raise NotImplementedError(f"{who} does not support a DCCRN built with use_clstm=False")
+
+
+def refuse_mask_mode(model, who):
+    """Consumers that have mask 'E' compiled in, or no parity test of their own with another mask
+    (the distillation steps, captured step graphs, the fused streaming hop), refuse a
+    DCCRN(masking_mode='C' or 'R')."""
+    mode = getattr(model, "masking_mode", "E")
+    if mode != "E":
+        raise NotImplementedError(f"{who} does not support a DCCRN built with masking_mode={mode!r}")
+
+
 def _pv(*tensors):
     """Cache key of a parameter group: storage pointers and in-place versions."""
     return tuple((t.data_ptr(), t._version) for t in tensors)
@@ -361,10 +385,23 @@ class DCCRN(nn.Module):
                  masking_mode="E", use_clstm=False, use_cbn=False, kernel_size=5,
                  kernel_num=[16, 32, 64, 128, 256, 256]):
         super().__init__()
-        if masking_mode != "E" or not use_clstm or kernel_size != 5:
+        if masking_mode not in ("E", "C", "R") or kernel_size != 5:
             raise NotImplementedError(
-                "clskd.DCCRN builds the DCCRN-CL path of the reference (masking_mode='E', "
-                "use_clstm=True, kernel_size=5; use_cbn False or True)")
+                "clskd.DCCRN builds the reference's kernel_size=5 models (masking_mode 'E', 'C' or "
+                "'R'; use_clstm and use_cbn False or True), not "
+                f"masking_mode={masking_mode!r}, kernel_size={kernel_size!r}")
+        if masking_mode == "C" and use_clstm:
+            # the one pairing of the family that stays refused: DCCRN(masking_mode='C',
+            # use_clstm=True) raising is existing behaviour that the suite holds (tests/test_abi.py,
+            # tests/test_cbn_ref_cpu.py); mask 'C' runs on the real LSTM
+            raise NotImplementedError(
+                "clskd.DCCRN does not build masking_mode='C' on the complex-LSTM stack "
+                "(use_clstm=True); mask 'C' runs with use_clstm=False, masks 'E' and 'R' with either")
+        if not use_clstm and rnn_units not in REAL_LSTM_UNITS:
+            raise NotImplementedError(
+                f"use_clstm=False: rnn_units={rnn_units} is the hidden size of the real LSTM and the "
+                f"recurrence is built for {REAL_LSTM_UNITS} (one workgroup holds W_hh in registers; "
+                "DESIGN.md)")
         if (win_len, win_inc, fft_len) != (400, 100, 512):
             raise NotImplementedError("clskd.DCCRN is built for win 400 / hop 100 / fft 512")
         self.win_len, self.win_inc, self.fft_len, self.win_type = win_len, win_inc, fft_len, win_type
@@ -374,7 +411,7 @@ class DCCRN(nn.Module):
         self.kernel_size = kernel_size
         self.kernel_num = [2] + list(kernel_num)
         self.masking_mode = masking_mode
-        self.use_clstm = use_clstm
+        self.use_clstm = bool(use_clstm)
         self.use_cbn = bool(use_cbn)
         norm = ComplexBatchNorm if use_cbn else nn.BatchNorm2d  # DCCRN.py:80,123
         self.fix = True
@@ -390,13 +427,19 @@ class DCCRN(nn.Module):
                 norm(kn[idx + 1]),
                 nn.PReLU()))
         hidden_dim = fft_len // (2 ** len(kn))
-        rnns = []
-        for idx in range(rnn_layers):
-            rnns.append(NavieComplexLSTM(
-                input_size=hidden_dim * kn[-1] if idx == 0 else rnn_units,
-                hidden_size=rnn_units,
-                projection_dim=hidden_dim * kn[-1] if idx == rnn_layers - 1 else None))
-        self.enhance = nn.Sequential(*rnns)
+        if use_clstm:
+            rnns = []
+            for idx in range(rnn_layers):
+                rnns.append(NavieComplexLSTM(
+                    input_size=hidden_dim * kn[-1] if idx == 0 else rnn_units,
+                    hidden_size=rnn_units,
+                    projection_dim=hidden_dim * kn[-1] if idx == rnn_layers - 1 else None))
+            self.enhance = nn.Sequential(*rnns)
+        else:  # DCCRN.py:101-109: two layers whatever rnn_layers says, and the name as written
+            self.enhance = nn.LSTM(input_size=hidden_dim * kn[-1], hidden_size=rnn_units,
+                                   num_layers=2, dropout=0.0, bidirectional=False,
+                                   batch_first=False)
+            self.tranform = nn.Linear(rnn_units, hidden_dim * kn[-1])
         for idx in range(len(kn) - 1, 0, -1):
             mods = [ComplexConvTranspose2d(kn[idx] * 2, kn[idx - 1], kernel_size=(kernel_size, 2),
                                            stride=(2, 1), padding=(2, 0), output_padding=(1, 0))]
@@ -531,7 +574,7 @@ class DCCRN(nn.Module):
             enc = [(s[0], s[1], s[2]) for s in self.encoder]
             dec = [(s[0], s[1] if len(s) > 1 else None, s[2] if len(s) > 1 else None)
                    for s in self.decoder]
-            self._refs = dict(enc=enc, dec=dec, lstm=list(self.enhance))
+            self._refs = dict(enc=enc, dec=dec, lstm=list(self.enhance) if self.use_clstm else None)
         return self._refs
 
     def _enc_w(self, i, compute="fp32"):
@@ -607,6 +650,33 @@ class DCCRN(nn.Module):
                 p += [m.r_trans.weight, m.r_trans.bias, m.i_trans.weight, m.i_trans.bias]
             return p
         return self._packed(("lstm", li, compute), ps, build)
+
+    def _rlstm_w(self, li, compute="fp32"):
+        """Packed operands of layer li of the real-LSTM bottleneck (use_clstm=False), in the
+        positions of _lstm_w: [wp, gate bias, whh [1][4H][H]] and, for the last layer, the
+        `tranform` projection's [wp, bias]."""
+        L = clstm.layer_view(self.enhance, li)
+        lin = self.tranform if li == 1 else None
+
+        def build():
+            wih = L.weight_ih_l0  # [4H, D]
+            if li == 0:  # the parameter's column order is (channel, f), the packed K order (f, channel)
+                D = wih.shape[1]
+                w = wih.reshape(wih.shape[0], D // 4, 4).permute(0, 2, 1)
+                wp = ops.pack_weight(w, D, compute)
+            else:
+                wp = ops.pack_weight(wih.unsqueeze(1), wih.shape[1], compute)
+            out = [wp, (L.bias_ih_l0 + L.bias_hh_l0).float().contiguous(),
+                   L.weight_hh_l0.unsqueeze(0).float().contiguous()]
+            if lin is not None:
+                out += [ops.pack_weight(lin.weight.unsqueeze(1), lin.weight.shape[1], compute),
+                        lin.bias.float().contiguous()]
+            return out
+
+        def ps():
+            p = [L.weight_ih_l0, L.weight_hh_l0, L.bias_ih_l0, L.bias_hh_l0]
+            return p + [lin.weight, lin.bias] if lin is not None else p
+        return self._packed(("rlstm", li, compute), ps, build)
 
     def _stft_w(self):
         def build():  # [514, 400] -> K padded to the fp32 engine's multiple
@@ -727,6 +797,21 @@ class DCCRN(nn.Module):
                                       f"'f32x3'), not compute={self.compute!r}")
         if cbn and torch.cuda.is_current_stream_capturing():
             raise NotImplementedError("a captured step graph does not support use_cbn=True")
+        if not self.use_clstm:
+            if gram_taps is not None:
+                refuse_real_lstm(self, "gram_taps (the tap contract has a complex clstm pair)")
+            if self.act_dtype != torch.float32:
+                raise NotImplementedError("use_clstm=False needs fp32 activations (compute 'fp32' "
+                                          f"or 'f32x3'), not compute={self.compute!r}")
+            if torch.cuda.is_current_stream_capturing():
+                refuse_real_lstm(self, "a captured step graph")
+        if self.masking_mode != "E":
+            if self.act_dtype != torch.float32:
+                raise NotImplementedError(
+                    f"masking_mode={self.masking_mode!r} needs fp32 activations (compute 'fp32' or "
+                    f"'f32x3'), not compute={self.compute!r}")
+            if torch.cuda.is_current_stream_capturing():
+                refuse_mask_mode(self, "a captured step graph")
         if not x.is_cuda:
             raise RuntimeError("clskd.DCCRN.forward needs inputs on the HIP device")
         x = x.float()
@@ -780,7 +865,7 @@ class DCCRN(nn.Module):
             mark("encoder done")
         if on_encoder is not None:
             on_encoder(enc)
-        # ---------------- complex LSTM (DCCRN.py:178-199, tools_for_model.py:159-174)
+        # ---------------- complex LSTM (DCCRN.py:178-199, tools_for_model.py:159-174) or LSTM
         C6 = kn[-1]
         Ch = C6 // 2
         act6 = enc[-1]
@@ -791,21 +876,34 @@ class DCCRN(nn.Module):
         # (one rounding, as every other teacher activation); fp32 models and taped
         # (backward) forwards keep fp32
         lo = act if (self.compute != "fp32" and tape is None) else f32
-        in0 = [([seg_bftc(act6, c0=half * Ch, C=Ch)], [(f, 0) for f in range(D4)])
-               for half in range(2)]
-        lstm_io = clstm.forward(in0, lambda li, segs: self._lstm_w(li, self._cmp(segs))[:3],
-                                self.hidden_layers, B, T, H, lo, _LSTM_CELLS, tape)
-        r_in = lstm_io[-1]
-        # projection into the decoder input [B][D4][T][C6] (DCCRN.py:188-199)
         dec_in = torch.empty(B, D4, T, C6, **act)
-        m = self._layer_refs()["lstm"][self.hidden_layers - 1]
-        P = m.projection_dim
-        for half in range(2):
-            segs = [Seg(r_in[half], 0, SegGeom(H, T * H, 0, H, 1, T))]
-            packs = self._lstm_w(self.hidden_layers - 1, self._cmp(segs, H))
-            wpp, bp = packs[3 + 2 * half], packs[4 + 2 * half]
-            ops.conv(segs, [(0, 0)], B, 1, T, P, wpp, bp,
-                     dec_in, OutMap(D4 * T * C6, 0, C6, 1, T * C6, D4), out_offset=half * Ch)
+        if not self.use_clstm:
+            # the real LSTM (DCCRN.py:192-197): one weight set x B sequences per layer, H =
+            # rnn_units, layer 0 reading the whole encoder output; `tranform` writes output
+            # feature c * D4 + d to dec_in[b][d][t][c]
+            H = self.rnn_units
+            in0 = [([seg_bftc(act6, 0, C6)], [(f, 0) for f in range(D4)])]
+            lstm_io = clstm.forward(in0, lambda li, segs: self._rlstm_w(li, self._cmp(segs))[:3],
+                                    2, B, T, H, f32, _LSTM_CELLS, tape)
+            segs = [Seg(lstm_io[-1][0], 0, SegGeom(H, T * H, 0, H, 1, T))]
+            packs = self._rlstm_w(1, self._cmp(segs, H))
+            ops.conv(segs, [(0, 0)], B, 1, T, D4 * C6, packs[3], packs[4], dec_in,
+                     OutMap(D4 * T * C6, 0, C6, 1, T * C6, D4))
+        else:
+            in0 = [([seg_bftc(act6, c0=half * Ch, C=Ch)], [(f, 0) for f in range(D4)])
+                   for half in range(2)]
+            lstm_io = clstm.forward(in0, lambda li, segs: self._lstm_w(li, self._cmp(segs))[:3],
+                                    self.hidden_layers, B, T, H, lo, _LSTM_CELLS, tape)
+            r_in = lstm_io[-1]
+            # projection into the decoder input [B][D4][T][C6] (DCCRN.py:188-199)
+            m = self._layer_refs()["lstm"][self.hidden_layers - 1]
+            P = m.projection_dim
+            for half in range(2):
+                segs = [Seg(r_in[half], 0, SegGeom(H, T * H, 0, H, 1, T))]
+                packs = self._lstm_w(self.hidden_layers - 1, self._cmp(segs, H))
+                wpp, bp = packs[3 + 2 * half], packs[4 + 2 * half]
+                ops.conv(segs, [(0, 0)], B, 1, T, P, wpp, bp,
+                         dec_in, OutMap(D4 * T * C6, 0, C6, 1, T * C6, D4), out_offset=half * Ch)
         if mark is not None:
             mark("lstm + projection done")
         if on_decoder_tap is not None:
@@ -865,14 +963,14 @@ class DCCRN(nn.Module):
                         enc=enc, dec=dec, dec_in=dec_in, spec=spec, est=None, T=T,
                         enc_nchw=[nchw(t) for t in enc], dec_nchw=[nchw(t) for t in dec],
                         lstm_io=lstm_io)
-        # ---------------- mask 'E' + ConviSTFT + clamp (DCCRN.py:207-237)
+        # ---------------- mask 'E' / 'C' / 'R' + ConviSTFT + clamp (DCCRN.py:207-237)
         mask = dec[-1]  # [B][256][T+1][2]
         est = torch.empty(B, T, 516, **f32)
         mr = mi = None
         if want_masks:
             mr = torch.empty(B, T, 257, **f32)
             mi = torch.empty(B, T, 257, **f32)
-        ops.mask_e(spec, mask, T, est, mr, mi)
+        ops.mask(self.masking_mode, spec, mask, T, est, mr, mi)
         winv, window = self._istft_w()
         frames = torch.empty(B, T, 400, **f32)
         ops.conv([Seg(est, 0, SegGeom(516, T * 516, 0, 516, 1, T))], [(0, 0)], B, 1, T, 400, winv,

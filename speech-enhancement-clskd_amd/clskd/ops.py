@@ -1018,6 +1018,20 @@ def mask_e(spec, mask, T, est, mask_r=None, mask_i=None):
                              est.shape[-1], ptr(mask_r), ptr(mask_i), _stream()), "mask_e")
 
 
+MASK_MODES = {"C": 1, "R": 2}  # CLSKD_MASK_C / CLSKD_MASK_R; 'E' has entries of its own
+
+
+def mask(mode, spec, mask, T, est, mask_r=None, mask_i=None):
+    """DCCRN.py:207-230 for masking_mode 'E', 'C' or 'R' (the arguments of mask_e)."""
+    if mode == "E":
+        return mask_e(spec, mask, T, est, mask_r, mask_i)
+    if mode not in MASK_MODES:
+        raise ValueError(f"masking_mode {mode!r}: 'E', 'C' or 'R'")
+    check(lib().clskd_mask_cr(MASK_MODES[mode], ptr(spec), spec.shape[-1], ptr(mask), mask.shape[2],
+                              spec.shape[0], T, ptr(est), est.shape[-1], ptr(mask_r), ptr(mask_i),
+                              _stream()), "mask_cr")
+
+
 def ola_hop(frames, window, hop, out_len, trim, clamp, wav):
     B, T, win = frames.shape
     check(lib().clskd_ola(ptr(frames), ptr(window), B, T, win, hop, out_len, trim, int(clamp),
@@ -1565,6 +1579,17 @@ def mask_e_bwd(spec, mask, T, dest, dmask):
     B = spec.shape[0]
     check(lib().clskd_mask_e_bwd(ptr(spec), spec.shape[-1], ptr(mask), mask.shape[2], B, T,
                                  ptr(dest), dest.shape[-1], ptr(dmask), _stream()), "mask_e_bwd")
+
+
+def mask_bwd(mode, spec, mask, T, dest, dmask):
+    """d est -> d mask for masking_mode 'E', 'C' or 'R' (the arguments of mask_e_bwd)."""
+    if mode == "E":
+        return mask_e_bwd(spec, mask, T, dest, dmask)
+    if mode not in MASK_MODES:
+        raise ValueError(f"masking_mode {mode!r}: 'E', 'C' or 'R'")
+    check(lib().clskd_mask_cr_bwd(MASK_MODES[mode], ptr(spec), spec.shape[-1], ptr(mask),
+                                  mask.shape[2], spec.shape[0], T, ptr(dest), dest.shape[-1],
+                                  ptr(dmask), _stream()), "mask_cr_bwd")
 
 
 def ola_bwd(frames, window, dwav, hop, out_len, trim, clamp, dframes):

@@ -26,7 +26,7 @@ import torch
 from . import clstm
 from . import config as cfg
 from . import ops
-from .model import refuse_cbn
+from .model import refuse_cbn, refuse_mask_mode, refuse_real_lstm
 from .ops import OutMap, Seg, SegGeom
 
 HOP, WIN = 100, 400
@@ -51,6 +51,7 @@ class StreamingDCCRN:
 
     def __init__(self, model, batch, graph=True):
         refuse_cbn(model, "StreamingDCCRN")
+        refuse_real_lstm(model, "StreamingDCCRN")
         if model.training:
             raise ValueError("StreamingDCCRN runs eval-mode BatchNorm: call model.eval() first")
         self.m = model
@@ -204,8 +205,8 @@ class StreamingDCCRN:
                 pr = m.decoder[d][2]
                 self._bn_apply(self.draw[d].view(B, 2 * F, Co), self.dwin[d + 1][1], self.dbn[d],
                                pr.weight)
-        # ---- mask 'E' on frame t-6, ConviSTFT frame, overlap-add (DCCRN.py:207-237)
-        ops.mask_e(self.spec[0].view(B, 1, 514), self.mask, 1, self.est)
+        # ---- mask 'E' / 'C' / 'R' on frame t-6, ConviSTFT frame, overlap-add (DCCRN.py:207-237)
+        ops.mask(m.masking_mode, self.spec[0].view(B, 1, 514), self.mask, 1, self.est)
         winv, window = m._istft_w()
         ops.conv([Seg(self.est, 0, SegGeom(516, 516, 0, 516, 1, 1))], [(0, 0)], B, 1, 1, WIN, winv,
                  None, self.frames, OutMap(4 * WIN, 0, 0), out_offset=3 * WIN)
@@ -272,6 +273,7 @@ class FusedStreamingDCCRN(StreamingDCCRN):
     re-create the object after changing the model's parameters)."""
 
     def __init__(self, model, batch):
+        refuse_mask_mode(model, "FusedStreamingDCCRN (mask 'E' is compiled into its hop kernel)")
         super().__init__(model, batch, graph=False)
         m, B, dev = self.m, self.B, self.dev
         from . import _lib

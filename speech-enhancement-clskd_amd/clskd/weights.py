@@ -78,6 +78,13 @@ def _value(seed, name, shape, shapes):
         w = shapes[name.rsplit(".", 1)[0] + ".weight"]
         k = 1.0 / np.sqrt(int(w[1]))
         return _f32(g.uniform(-k, k, shape))
+    if name.startswith("enhance.weight_") or name.startswith("enhance.bias_"):
+        # DCCRN(use_clstm=False): one two-layer nn.LSTM, U(-1/sqrt(H), 1/sqrt(H)), H = rows/4
+        k = 1.0 / np.sqrt(shape[0] // 4)
+        return _f32(g.uniform(-k, k, shape))
+    if name.startswith("tranform."):  # its nn.Linear (the reference's spelling): 1/sqrt(in_features)
+        k = 1.0 / np.sqrt(int(shapes["tranform.weight"][1]))
+        return _f32(g.uniform(-k, k, shape))
     if "_conv.weight" in name:
         return _f32(0.05 * g.standard_normal(shape))
     if "_conv.bias" in name:

@@ -288,5 +288,27 @@ __device__ __forceinline__ void mask_tile_load(const float* __restrict__ mcol, i
     if (r < 2 * nt) ml[fm * MASK_LD + r] = mcol[(int64_t)fm * Tm * 2 + r];
   }
 }
+// the backward twin: dcol[fm * Tm * 2 + r] = ml[fm][r] for r < 2 * nt (the mask gradient of the
+// block's frames, in the same runs), and for the block with first = true the columns of the
+// utterance's mask (dutt: its [256][Tm][2]) that no frame reads — tm = 0 and T < tm < Tm — as zero.
+// For blocks of 256 threads (the mask backward kernels' launch bounds).
+__device__ __forceinline__ void mask_tile_store(float* __restrict__ dcol, float* __restrict__ dutt,
+                                                int Tm, int T, int nt, bool first,
+                                                const float* ml) {
+  for (int i = threadIdx.x; i < 256 * 2 * MASK_TT; i += 256) {
+    const int fm = i / (2 * MASK_TT), r = i - fm * 2 * MASK_TT;
+    if (r < 2 * nt) dcol[(int64_t)fm * Tm * 2 + r] = ml[fm * MASK_LD + r];
+  }
+  if (first) {
+    const int nz = Tm - T;
+    for (int i = threadIdx.x; i < 256 * nz; i += 256) {
+      const int fm = i / nz, j = i - fm * nz;
+      const int tm = j == 0 ? 0 : T + j;
+      float* dp = dutt + ((int64_t)fm * Tm + tm) * 2;
+      dp[0] = 0.f;
+      dp[1] = 0.f;
+    }
+  }
+}
 
 }  // namespace clskd

@@ -242,6 +242,39 @@ __global__ __launch_bounds__(256) void mask_e_kernel(const float* __restrict__ s
   }
 }
 
+// masking modes 'C' and 'R' (DCCRN.py:227-230) on mask_e_kernel's tiling and layouts:
+//   'C' (CPLX): est = spec * mask as complex numbers;  'R': est_re = re mr, est_im = im mi.
+template <bool CPLX>
+__global__ __launch_bounds__(256) void mask_cr_kernel(const float* __restrict__ spec, int ldspec,
+                                                      const float* __restrict__ mask, int Tm, int B,
+                                                      int T, float* __restrict__ est, int ldest,
+                                                      float* __restrict__ mask_r,
+                                                      float* __restrict__ mask_i) {
+  __shared__ __attribute__((aligned(16))) float ml[256 * MASK_LD];
+  const int b = blockIdx.y, t0 = blockIdx.x * MASK_TT;
+  const int nt = min(MASK_TT, T - t0);
+  mask_tile_load(mask + ((int64_t)b * 256 * Tm + t0 + 1) * 2, Tm, nt, ml);
+  __syncthreads();
+  for (int i = threadIdx.x; i < nt * 257; i += 256) {
+    const int tt = i / 257, f = i - tt * 257;
+    const int64_t bt = (int64_t)b * T + t0 + tt;
+    const float re = spec[bt * ldspec + f];
+    const float im = spec[bt * ldspec + 257 + f];
+    float mr = 0.f, mi = 0.f;
+    if (f > 0) {
+      mr = ml[(f - 1) * MASK_LD + 2 * tt];
+      mi = ml[(f - 1) * MASK_LD + 2 * tt + 1];
+    }
+    est[bt * ldest + f] = CPLX ? re * mr - im * mi : re * mr;
+    est[bt * ldest + 257 + f] = CPLX ? re * mi + im * mr : im * mi;
+    if (f < ldest - 514) est[bt * ldest + 514 + f] = 0.f;
+    if (mask_r) {
+      mask_r[bt * 257 + f] = mr;
+      mask_i[bt * 257 + f] = mi;
+    }
+  }
+}
+
 // asteroid DCCRNet: mask = tanh(|M|) e^{i angle(M)} (complex_nn.BoundComplexMask('tanh')), est =
 // mask * X on bins 0..255 (the Nyquist bin was dropped before the masker and is padded back as
 // zero); mask BFTC [B][256][Tm][2] read at t, spectrum / est rows [B][T][ld] (re 0.., im 257..)
@@ -629,6 +662,28 @@ extern "C" int clskd_mask_e(const float* spec, int32_t ldspec, const float* mask
   hipLaunchKernelGGL(mask_e_kernel, dim3((unsigned)cdiv(T, MASK_TT), (unsigned)B), dim3(256), 0,
                      as_stream(stream), spec, ldspec, mask, Tm, B, T, est, ldest, mask_r, mask_i);
   CLSKD_LAUNCH_CHECK("mask_e");
+  return CLSKD_OK;
+}
+
+extern "C" int clskd_mask_cr(int32_t mode, const float* spec, int32_t ldspec, const float* mask,
+                             int32_t Tm, int32_t B, int32_t T, float* est, int32_t ldest,
+                             float* mask_r, float* mask_i, void* stream) {
+  CLSKD_CHECK_ARG(spec && mask && est, "mask_cr: null pointer");
+  CLSKD_CHECK_ARG(!mask_r == !mask_i, "mask_cr: mask_r and mask_i come together");
+  CLSKD_CHECK_SHAPE(mode == CLSKD_MASK_C || mode == CLSKD_MASK_R, "mask_cr: mode=%d", mode);
+  CLSKD_CHECK_SHAPE(ldspec >= 514, "mask_cr: ldspec=%d < 514", ldspec);
+  CLSKD_CHECK_SHAPE(ldest >= 514 && ldest - 514 <= 257, "mask_cr: ldest=%d outside [514, 771]",
+                    ldest);
+  CLSKD_CHECK_SHAPE(Tm >= T + 1, "mask_cr: Tm=%d < T+1", Tm);
+  CLSKD_CHECK_SHAPE(B > 0 && B <= 65535 && T > 0, "mask_cr: B=%d T=%d", B, T);
+  const dim3 grid((unsigned)cdiv(T, MASK_TT), (unsigned)B);
+  if (mode == CLSKD_MASK_C)
+    hipLaunchKernelGGL(mask_cr_kernel<true>, grid, dim3(256), 0, as_stream(stream), spec, ldspec,
+                       mask, Tm, B, T, est, ldest, mask_r, mask_i);
+  else
+    hipLaunchKernelGGL(mask_cr_kernel<false>, grid, dim3(256), 0, as_stream(stream), spec, ldspec,
+                       mask, Tm, B, T, est, ldest, mask_r, mask_i);
+  CLSKD_LAUNCH_CHECK("mask_cr");
   return CLSKD_OK;
 }
 

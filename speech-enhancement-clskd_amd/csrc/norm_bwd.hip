@@ -459,20 +459,33 @@ __global__ __launch_bounds__(256) void mask_e_bwd_kernel(const float* __restrict
     mp[1] = gi;
   }
   __syncthreads();
-  for (int i = threadIdx.x; i < 256 * 2 * MASK_TT; i += 256) {
-    const int fm = i / (2 * MASK_TT), r = i - fm * 2 * MASK_TT;
-    if (r < 2 * nt) dmask[col0 + (int64_t)fm * Tm * 2 + r] = ml[fm * MASK_LD + r];
+  mask_tile_store(dmask + col0, dmask + (int64_t)b * 256 * Tm * 2, Tm, T, nt, blockIdx.x == 0, ml);
+}
+
+// masking modes 'C' and 'R' backward (DCCRN.py:227-230), d est -> d mask on the tiling above:
+//   'C' (CPLX): dmr = dre re + dim im, dmi = dim re - dre im;  'R': dmr = dre re, dmi = dim im
+template <bool CPLX>
+__global__ __launch_bounds__(256) void mask_cr_bwd_kernel(const float* __restrict__ spec,
+                                                          int ldspec, int Tm, int B, int T,
+                                                          const float* __restrict__ dest,
+                                                          int ldest, float* __restrict__ dmask) {
+  __shared__ __attribute__((aligned(16))) float ml[256 * MASK_LD];
+  const int b = blockIdx.y, t0 = blockIdx.x * MASK_TT;
+  const int nt = min(MASK_TT, T - t0);
+  const int64_t col0 = ((int64_t)b * 256 * Tm + t0 + 1) * 2;
+  for (int i = threadIdx.x; i < nt * 256; i += 256) {
+    const int tt = i >> 8, fm = i & 255;
+    const int f = fm + 1;
+    const int64_t bt = (int64_t)b * T + t0 + tt;
+    const float re = spec[bt * ldspec + f];
+    const float im = spec[bt * ldspec + 257 + f];
+    const float dre = dest[bt * ldest + f], dim = dest[bt * ldest + 257 + f];
+    float* mp = ml + fm * MASK_LD + 2 * tt;
+    mp[0] = CPLX ? dre * re + dim * im : dre * re;
+    mp[1] = CPLX ? dim * re - dre * im : dim * im;
   }
-  if (blockIdx.x == 0) {  // columns without a gradient: tm = 0 and T < tm < Tm
-    const int nz = Tm - T;
-    for (int i = threadIdx.x; i < 256 * nz; i += 256) {
-      const int fm = i / nz, j = i - fm * nz;
-      const int tm = j == 0 ? 0 : T + j;
-      float* dp = dmask + (((int64_t)b * 256 + fm) * Tm + tm) * 2;
-      dp[0] = 0.f;
-      dp[1] = 0.f;
-    }
-  }
+  __syncthreads();
+  mask_tile_store(dmask + col0, dmask + (int64_t)b * 256 * Tm * 2, Tm, T, nt, blockIdx.x == 0, ml);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1064,6 +1077,27 @@ extern "C" int clskd_mask_e_bwd(const float* spec, int32_t ldspec, const float* 
   hipLaunchKernelGGL(mask_e_bwd_kernel, dim3((unsigned)cdiv(T, MASK_TT), (unsigned)B), dim3(256), 0,
                      as_stream(stream), spec, ldspec, mask, Tm, B, T, dest, ldest, dmask);
   CLSKD_LAUNCH_CHECK("mask_e_bwd");
+  return CLSKD_OK;
+}
+
+extern "C" int clskd_mask_cr_bwd(int32_t mode, const float* spec, int32_t ldspec, const float* mask,
+                                 int32_t Tm, int32_t B, int32_t T, const float* dest,
+                                 int32_t ldest, float* dmask, void* stream) {
+  CLSKD_CHECK_ARG(spec && mask && dest && dmask, "mask_cr_bwd: null pointer");
+  CLSKD_CHECK_SHAPE(mode == CLSKD_MASK_C || mode == CLSKD_MASK_R, "mask_cr_bwd: mode=%d", mode);
+  CLSKD_CHECK_SHAPE(ldspec >= 514, "mask_cr_bwd: ldspec=%d < 514", ldspec);
+  CLSKD_CHECK_SHAPE(ldest >= 514, "mask_cr_bwd: ldest=%d < 514", ldest);
+  CLSKD_CHECK_SHAPE(Tm >= T + 1, "mask_cr_bwd: Tm=%d < T+1", Tm);
+  CLSKD_CHECK_SHAPE(B > 0 && B <= 65535 && T > 0, "mask_cr_bwd: B=%d T=%d", B, T);
+  // both products are linear in the mask: its values are not read
+  const dim3 grid((unsigned)cdiv(T, MASK_TT), (unsigned)B);
+  if (mode == CLSKD_MASK_C)
+    hipLaunchKernelGGL(mask_cr_bwd_kernel<true>, grid, dim3(256), 0, as_stream(stream), spec,
+                       ldspec, Tm, B, T, dest, ldest, dmask);
+  else
+    hipLaunchKernelGGL(mask_cr_bwd_kernel<false>, grid, dim3(256), 0, as_stream(stream), spec,
+                       ldspec, Tm, B, T, dest, ldest, dmask);
+  CLSKD_LAUNCH_CHECK("mask_cr_bwd");
   return CLSKD_OK;
 }
 
