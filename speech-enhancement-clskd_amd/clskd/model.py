@@ -213,6 +213,7 @@ def refuse_cbn(model, who):
 
 
 REAL_LSTM_UNITS = (16, 32, 64, 128)  # hidden sizes csrc/lstm.hip is built for
+MAX_LAYERS = 8  # encoder / decoder depth: 256 / 2^8 = 1 frequency bin left for the LSTM
 
 
 def refuse_real_lstm(model, who):
@@ -404,6 +405,27 @@ class DCCRN(nn.Module):
                 "DESIGN.md)")
         if (win_len, win_inc, fft_len) != (400, 100, 512):
             raise NotImplementedError("clskd.DCCRN is built for win 400 / hop 100 / fft 512")
+        kernel_num = list(kernel_num)
+        if not 1 <= len(kernel_num) <= MAX_LAYERS:
+            # every encoder layer halves the 256 bins; the LSTM needs at least one left
+            raise NotImplementedError(
+                f"kernel_num has {len(kernel_num)} entries: the depth is 1 to {MAX_LAYERS} layers "
+                f"(256 / 2^depth frequency bins reach the LSTM, at least one)")
+        if any(int(c) != c or c < 8 or c % 8 or c > 1024 for c in kernel_num):
+            # csrc/norm.hip, csrc/cbn.hip: the apply passes move 8 channels per item (and the
+            # statistics pass holds at most 1024 per row); 8 | C also keeps every segment of the
+            # fp32 conv engines on 16-byte runs, the halves of the complex stack's kernel_num[-1]
+            # included
+            raise NotImplementedError(
+                f"kernel_num={kernel_num}: every entry is a multiple of 8 between 8 and 1024 (the "
+                "normalisation kernels move 8 channels per item)")
+        if use_clstm and (rnn_units % 2 or rnn_units // 2 not in REAL_LSTM_UNITS):
+            raise NotImplementedError(
+                f"use_clstm=True: rnn_units={rnn_units} gives the real and imaginary LSTMs "
+                f"rnn_units / 2 hidden units each, and the recurrence is built for "
+                f"{REAL_LSTM_UNITS}: rnn_units is one of {tuple(2 * h for h in REAL_LSTM_UNITS)}")
+        if use_clstm and rnn_layers < 1:
+            raise NotImplementedError(f"use_clstm=True: rnn_layers={rnn_layers} is at least 1")
         self.win_len, self.win_inc, self.fft_len, self.win_type = win_len, win_inc, fft_len, win_type
         self.rnn_units = rnn_units
         self.input_dim = self.output_dim = win_len
@@ -426,7 +448,7 @@ class DCCRN(nn.Module):
                               padding=(2, 1)),
                 norm(kn[idx + 1]),
                 nn.PReLU()))
-        hidden_dim = fft_len // (2 ** len(kn))
+        self.hidden_dim = hidden_dim = fft_len // (2 ** len(kn))  # bins left after the encoder (D4)
         if use_clstm:
             rnns = []
             for idx in range(rnn_layers):
@@ -629,9 +651,8 @@ class DCCRN(nn.Module):
             H = R.hidden_size
             wih = torch.cat([R.weight_ih_l0, I.weight_ih_l0], 0)  # [8H, D]
             if li == 0:
-                D = wih.shape[1]
-                Ch = D // 4
-                w = wih.reshape(8 * H, Ch, 4).permute(0, 2, 1)  # [8H, tap=f, Ch]
+                D, D4 = wih.shape[1], self.hidden_dim
+                w = wih.reshape(8 * H, D // D4, D4).permute(0, 2, 1)  # [8H, tap=f, Ch]
                 wp = ops.pack_weight(w, D, compute)
             else:
                 wp = ops.pack_weight(wih.unsqueeze(1), wih.shape[1], compute)
@@ -661,8 +682,8 @@ class DCCRN(nn.Module):
         def build():
             wih = L.weight_ih_l0  # [4H, D]
             if li == 0:  # the parameter's column order is (channel, f), the packed K order (f, channel)
-                D = wih.shape[1]
-                w = wih.reshape(wih.shape[0], D // 4, 4).permute(0, 2, 1)
+                D, D4 = wih.shape[1], self.hidden_dim
+                w = wih.reshape(wih.shape[0], D // D4, D4).permute(0, 2, 1)
                 wp = ops.pack_weight(w, D, compute)
             else:
                 wp = ops.pack_weight(wih.unsqueeze(1), wih.shape[1], compute)

@@ -287,7 +287,7 @@ def conv_mblocks(B, Fo, To):
 class _ConvPlan:
     """Launch descriptor of one conv signature, built once; per call only the pointers change."""
     __slots__ = ("desc", "segs", "nseg", "direct", "name", "fn", "flops", "bytes", "shape", "nstats",
-                 "osize", "fold")
+                 "osize", "fold", "ktab")
 
 
 _CONV_PLANS = {}
@@ -351,6 +351,9 @@ def _conv_plan(key, segs, geoms, taps, B, Fo, To, N, wpacked, bias, out, omap, s
     d.wlayout = _lib.WLAYOUT_DIRECT if direct else _lib.WLAYOUT_NK
     pl = _ConvPlan()
     pl.desc, pl.nseg, pl.direct = d, len(segs), direct
+    # the descriptor holds the K table by address: the plan owns the tensors (_ktab's cache is
+    # bounded, and a table it drops would otherwise be freed under every plan that points at it)
+    pl.ktab = (kt, ks)
     pl.segs = [d.seg[i] for i in range(_lib.MAX_SEGS)]  # views into d (patched per call)
     pl.name = None  # kernel instance the library dispatches to (read after the first launch)
     pl.fn = None  # its host function (the executor times launches by it)
@@ -1412,9 +1415,9 @@ def conv_wgrad(segs, taps, B, Fo, To, N, dy, omap, dw, dbias=None, dy_offset=0, 
         d.in_dtype = d.out_dtype = _lib.F32
         d.compute = _lib.F32X3 if split else _lib.F32
         ws = int(lib().clskd_conv2d_wgrad_workspace(d))
-        pl = (d, Kp, ws)
+        pl = (d, Kp, ws, (kt, ks))  # (the plan owns the K table its descriptor points at)
         _WGRAD_PLANS[key] = pl
-    d, Kp, ws = pl
+    d, Kp, ws, _ = pl
     assert dw.shape == (N, Kp) and dw.dtype == torch.float32 and dw.is_contiguous(), (dw.shape, N, Kp)
     for i, a in enumerate(addrs):
         d.seg[i].ptr = a

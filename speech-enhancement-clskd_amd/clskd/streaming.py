@@ -30,7 +30,8 @@ from .model import refuse_cbn, refuse_mask_mode, refuse_real_lstm
 from .ops import OutMap, Seg, SegGeom
 
 HOP, WIN = 100, 400
-LOOKAHEAD = 6  # decoder frames: layer d reads its input one frame ahead, 6 layers
+LOOKAHEAD = 6  # decoder frames: layer d reads its input one frame ahead, 6 layers (a DCCRN of
+# another depth looks ahead by its own layer count: StreamingDCCRN.lookahead)
 LATENCY_HOPS = LOOKAHEAD + 3  # + the 300-sample centring of the STFT framing
 
 
@@ -61,6 +62,7 @@ class StreamingDCCRN:
         f32 = dict(device=dev, dtype=torch.float32)
         kn = model.kernel_num
         self.nl = nl = len(kn) - 1
+        self.lookahead = nl  # one frame per decoder layer (LOOKAHEAD for the six-layer models)
         self.H = H = model.rnn_units // 2
         C6 = kn[-1]
         self.D4 = D4 = 256 // (2 ** nl)
@@ -69,13 +71,14 @@ class StreamingDCCRN:
         self.wav_out = torch.zeros(B, HOP, **f32)
         self.xwin = torch.zeros(B, WIN, **f32)
         self.xtmp = torch.zeros(B, WIN - HOP, **f32)
-        self.spec = torch.zeros(LOOKAHEAD + 1, B, 514, **f32)     # spectra t-6 .. t
+        self.spec = torch.zeros(nl + 1, B, 514, **f32)            # spectra t-nl .. t
         self.spec_b = torch.zeros(B, 256, 1, 2, **f32)            # encoder-0 input frame (BFTC)
         Fi = [256 // (2 ** i) for i in range(nl + 1)]
         Cin = [2] + list(kn[1:-1])
         self.ewin = [torch.zeros(2, B, Fi[i], Cin[i], **f32) for i in range(nl)]   # enc inputs
         self.eraw = [torch.zeros(B, Fi[i + 1], 1, kn[i + 1], **f32) for i in range(nl)]
-        # encoder output ring of depth 7 - i: decoder layer 5 - i reads frames (t-6+i, t-5+i)
+        # encoder output ring of depth nl + 1 - i: decoder layer nl - 1 - i reads frames
+        # (t-nl+i, t-nl+1+i)
         self.ering = [torch.zeros(nl + 1 - i, B, Fi[i + 1], kn[i + 1], **f32) for i in range(nl)]
         self.gx = torch.zeros(2, B, 8 * H, **f32)
         self.h = torch.zeros(model.hidden_layers, 2, 2 * B, H, **f32)
@@ -205,7 +208,7 @@ class StreamingDCCRN:
                 pr = m.decoder[d][2]
                 self._bn_apply(self.draw[d].view(B, 2 * F, Co), self.dwin[d + 1][1], self.dbn[d],
                                pr.weight)
-        # ---- mask 'E' / 'C' / 'R' on frame t-6, ConviSTFT frame, overlap-add (DCCRN.py:207-237)
+        # ---- mask 'E' / 'C' / 'R' on frame t-nl, ConviSTFT frame, overlap-add (DCCRN.py:207-237)
         ops.mask(m.masking_mode, self.spec[0].view(B, 1, 514), self.mask, 1, self.est)
         winv, window = m._istft_w()
         ops.conv([Seg(self.est, 0, SegGeom(516, 516, 0, 516, 1, 1))], [(0, 0)], B, 1, 1, WIN, winv,
@@ -240,7 +243,7 @@ class StreamingDCCRN:
         else:
             self._hop()
         self.steps_run += 1
-        return self.wav_out.clone() if self.t - 1 - LOOKAHEAD >= 3 else None
+        return self.wav_out.clone() if self.t - 1 - self.lookahead >= 3 else None
 
     def process(self, x):
         """Whole clip x [B][L] (L % 100 == 0) through the hop loop + flush -> [B][L], aligned
@@ -255,7 +258,7 @@ class StreamingDCCRN:
             y = self.step(hop)
             if y is not None:
                 outs.append(y)
-        for _ in range(LOOKAHEAD):   # drain the decoder look-ahead with zero frames (eager)
+        for _ in range(self.lookahead):   # drain the decoder look-ahead with zero frames (eager)
             self.x_in.zero_()
             self._hop(live_in=False, zero_from=T)
             outs.append(self.wav_out.clone())
@@ -281,6 +284,11 @@ class FusedStreamingDCCRN(StreamingDCCRN):
         if nl != 6 or m.hidden_layers != 2:
             raise NotImplementedError("the fused hop is built for the 6-layer, 2-LSTM DCCRN")
         kn = m.kernel_num
+        if any(c & (c - 1) for c in kn[1:]):
+            # csrc/stream_hop.hip deals each layer's outputs to lanes by shifts and masks of the
+            # channel count: it checks this at the first launch; say it here, by name
+            raise NotImplementedError(
+                f"the fused hop is built for power-of-two widths, not kernel_num={kn[1:]}")
         C6 = kn[-1]
         keep = []
 

@@ -68,9 +68,14 @@ class SupervisedTraining(nn.Module):
     """A model trained on (noisy, clean) pairs with one DCCRN.loss mode: the step signatures of
     ``KnowledgeDistillation`` / ``OutputDistillation`` without a teacher.
 
-    model: a ``clskd.DCCRN`` in the student configuration (config.kernel_num_student,
-    rnn_units_student; ``use_cbn`` False or True: the taped forward and ``dccrn_backward`` route a
-    ComplexBatchNorm model through csrc/cbn.hip) or a ``DCCRNet_mini``.
+    model: a ``clskd.DCCRN`` — the student configuration (config.kernel_num_student,
+    rnn_units_student) on either LSTM stack, or on the complex stack any other one that constructs
+    (tests/test_gpu_configs.py holds the gradients of other widths, depths and LSTM layer counts
+    to the same gates) except the teacher configuration.  The teacher configuration (DESIGN.md
+    §18) and the reference's default widths on the real LSTM (§24) each missed that gate in
+    their trial and raise NotImplementedError; ``use_cbn`` False or True:
+    the taped forward and ``dccrn_backward`` route a ComplexBatchNorm model through csrc/cbn.hip —
+    or a ``DCCRNet_mini``.
     loss_mode: a DCCRN.loss mode (LOSS_MODES) or 'MRSTFT'.  For a DCCRNet_mini the LMS modes raise
     NotImplementedError (mini_backward has no entry point at the masked spectrum)."""
 
@@ -84,11 +89,21 @@ class SupervisedTraining(nn.Module):
         if self.is_mini and self.uses_lms:
             raise NotImplementedError(
                 f"loss_mode {loss_mode!r}: DCCRNet_mini's backward has no masked-spectrum entry point")
-        if not self.is_mini and (list(model.kernel_num[1:]) != list(cfg.kernel_num_student)
-                                 or model.rnn_units != cfg.rnn_units_student):
+        if not self.is_mini and (list(model.kernel_num[1:]) == list(cfg.kernel_num)
+                                 and model.rnn_units == cfg.rnn_units and model.use_clstm):
             raise NotImplementedError(
-                "SupervisedTraining: only the student DCCRN configuration is supported; the teacher "
-                "configuration missed the end-to-end gradient gate in its one trial (DESIGN.md §18)")
+                "SupervisedTraining: the teacher DCCRN configuration (kernel_num "
+                f"{list(cfg.kernel_num)}, rnn_units {cfg.rnn_units}) is not supported: it missed "
+                "the end-to-end gradient gate in its one trial (DESIGN.md §18)")
+        if not self.is_mini and not model.use_clstm and (
+                list(model.kernel_num[1:]) != list(cfg.kernel_num_student)
+                or model.rnn_units != cfg.rnn_units_student):
+            raise NotImplementedError(
+                f"SupervisedTraining: use_clstm=False with kernel_num {list(model.kernel_num[1:])}, "
+                f"rnn_units {model.rnn_units} is not supported: on the real-LSTM stack only the "
+                f"student configuration (kernel_num {list(cfg.kernel_num_student)}, rnn_units "
+                f"{cfg.rnn_units_student}) is held to the end-to-end gradient gate; the reference's "
+                "default widths missed it in their trial (DESIGN.md §24)")
         self.automatic_optimization = True
         self.student = model  # the trained model, under the name the shared helpers use
         self.student.compute = "fp32"
@@ -192,7 +207,8 @@ class SupervisedTraining(nn.Module):
             mini_backward(self.student, tp["s"], d_wav, grads, acc_params=accumulate)
             return
         enc, dec, dec_in = fwd["enc"], fwd["dec"], fwd["dec_in"]
-        g = dict(enc=[_zeros(t.shape, dev) for t in enc], dec=[_zeros(t.shape, dev) for t in dec[:5]],
+        # (every decoder output but the last: the mask's gradient comes from the waveform tail)
+        g = dict(enc=[_zeros(t.shape, dev) for t in enc], dec=[_zeros(t.shape, dev) for t in dec[:-1]],
                  dec_in=_zeros(dec_in.shape, dev), wav=d_wav, est_spec=d_est)
         dccrn_backward(self.student, tp["s"], enc, dec, dec_in, fwd["lstm_io"], g, grads,
                        acc_params=accumulate)

@@ -228,6 +228,63 @@ def spec_bftc(spec, re0, im0, Fn):
 
 
 # ------------------------------------------------------------------------------------------
+# BatchNorm + PReLU over rows of C channels (csrc/norm.hip, csrc/common.h:bn_channel_coeffs)
+# ------------------------------------------------------------------------------------------
+BN_CHANNELS = (8, 24, 40, 72, 200)   # C/8 = 1, 3, 5, 9, 25 and C/4 = 2, 6, 10, 18, 50
+BN_ROWS = (1, 37, 4864)              # one row; fewer rows than row lanes; several blocks
+# C/8 = 3 does not divide the apply kernel's largest grid stride (4096 x 256 items), and only
+# above that many items does a lane visit a second item and so another channel group
+BN_APPLY_LARGE = (349589, 24)        # rows x 3 items = 4096 x 256 + 191
+
+
+def bn_affine(x, scale, shift, alpha=None, alpha_im=None):
+    """y = x scale + shift per channel, then PReLU with one slope — or, with alpha_im, alpha on
+    the first half of the channels (real) and alpha_im on the second (imaginary)."""
+    y = x * scale + shift
+    if alpha is None:
+        return y
+    if alpha_im is None:
+        return torch.where(y >= 0, y, alpha * y)
+    h = x.shape[-1] // 2
+    return torch.cat([torch.where(y[..., :h] >= 0, y[..., :h], alpha * y[..., :h]),
+                      torch.where(y[..., h:] >= 0, y[..., h:], alpha_im * y[..., h:])], -1)
+
+
+def bn_coeffs(mean, var, gamma, beta, eps):
+    scale = gamma * torch.rsqrt(var + eps)
+    return scale, beta - mean * scale
+
+
+def batch_norm_train(x, gamma, beta, rm, rv, eps, momentum, alpha=None):
+    """nn.BatchNorm2d train forward over x [rows][C]: batch mean and biased variance, the
+    [scale | shift] coefficients, y (+ PReLU) and one running update (the unbiased variance; for
+    one row, where that is undefined, the biased one — 0 — takes its place, as the kernel does)."""
+    n = x.shape[0]
+    mean = x.mean(0)
+    var = ((x - mean) ** 2).mean(0)
+    scale, shift = bn_coeffs(mean, var, gamma, beta, eps)
+    unb = var * n / (n - 1) if n > 1 else var
+    return dict(mean=mean, var=var, scale=scale, shift=shift, y=bn_affine(x, scale, shift, alpha),
+                rm=(1 - momentum) * rm + momentum * mean, rv=(1 - momentum) * rv + momentum * unb)
+
+
+def batch_norm_eval(x, gamma, beta, rm, rv, eps, alpha=None):
+    scale, shift = bn_coeffs(rm, rv, gamma, beta, eps)
+    return dict(scale=scale, shift=shift, y=bn_affine(x, scale, shift, alpha))
+
+
+def bn_inputs(rows, C, seed=0):
+    """fp32 CPU tensors: x [rows][C] with a per-channel level and spread, the affine parameters,
+    non-trivial running statistics and [scale | shift] coefficients of mixed sign."""
+    g = _gen(6000 + seed + 7 * C + rows % 1000)
+    rn = lambda *s: torch.randn(*s, generator=g)
+    x = rn(rows, C) * (0.5 + torch.rand(C, generator=g)) + 0.5 * rn(C)
+    return dict(x=x.contiguous(), gamma=1.0 + 0.3 * rn(C), beta=0.2 * rn(C), rm=0.3 * rn(C),
+                rv=0.5 + torch.rand(C, generator=g), scale=(0.5 + rn(C).abs()) * torch.sign(rn(C)),
+                shift=0.5 * rn(C))
+
+
+# ------------------------------------------------------------------------------------------
 # SPKD (framework.py:150-172)
 # ------------------------------------------------------------------------------------------
 def spkd_from_grams(Gs, Gt, batchmean, scale):

@@ -343,21 +343,22 @@ def mini_steps(modes, x, y, dtype=torch.float64):
     return out
 
 
-def is_pre_bn_bias(name):
-    """Conv biases in front of a train-mode BatchNorm: analytically zero gradient (the project's
-    existing rule, tests/test_gpu_backward.py:_compare)."""
-    return name.endswith("_conv.bias") and not name.startswith("decoder.5.")
+def is_pre_bn_bias(name, n_layers=6):
+    """Conv biases in front of a train-mode normalisation: analytically zero gradient (the
+    project's existing rule, tests/test_gpu_backward.py:_compare).  A normalisation follows every
+    conv but the last decoder layer's (decoder.{n_layers - 1}, DCCRN.py:111-145)."""
+    return name.endswith("_conv.bias") and not name.startswith(f"decoder.{n_layers - 1}.")
 
 
-def grad_errors(got, ref):
+def grad_errors(got, ref, n_layers=6):
     """{name: (error, kind)}: relative L2, or for a pre-BN conv bias max(|got|, |ref|) / |dW ref|
-    (gate 1e-3, as tests/test_gpu_backward.py)."""
+    (gate 1e-3, as tests/test_gpu_backward.py).  n_layers: the model's encoder / decoder depth."""
     out = {}
     for n, r in ref.items():
         if r is None:
             continue
         g, r = got[n].double(), r.double()
-        if is_pre_bn_bias(n):
+        if is_pre_bn_bias(n, n_layers):
             wref = ref[n.replace(".bias", ".weight")].double().norm()
             out[n] = (float(max(g.norm(), r.norm()) / wref), "zero")
         else:

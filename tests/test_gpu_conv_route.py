@@ -49,3 +49,46 @@ def test_launch_runs_the_routed_engine(case, monkeypatch):
     print(case, route.decode(), kernel)
     assert route.decode() == engine
     assert kernel.split("<")[0] == KERNEL[engine]
+
+
+def test_launch_plans_own_their_k_tables(monkeypatch):
+    """A descriptor holds its K table by address, and ops._ktab's cache is bounded: a process that
+    plans more than its 1024 signatures (a long suite, variable clip lengths) drops tables that
+    cached plans still point at.  The plan keeps the tensors, so a launch after the cache has let
+    go of them (and the freed memory has been handed out again) gives the first launch's bits —
+    for the forward plan and the weight-gradient plan."""
+    import gc
+
+    from clskd import ops
+    monkeypatch.setattr(ops, "_CONV_PLANS", {})
+    monkeypatch.setattr(ops, "_WGRAD_PLANS", {})
+    ops._ktab.cache_clear()
+    B, F, Tn, Ci, N = 2, 8, 7, 24, 40
+    taps = [(kf - 2, kt - 1) for kf in range(5) for kt in range(2)]
+    g = torch.Generator().manual_seed(5)
+    x = torch.randn(B, F, Tn, Ci, generator=g).to(DEV)
+    dy = torch.randn(B, F, Tn, N, generator=g).to(DEV)
+    K = len(taps) * Ci
+    wp = ops.pack_weight(torch.randn(N, len(taps), Ci, generator=g).to(DEV) / K ** 0.5, K)
+    omap = ops.OutMap(F * Tn * N, Tn * N, N)
+
+    def launch():
+        out = torch.zeros(B, F, Tn, N, device=DEV)
+        ops.conv([ops.seg_bftc(x)], taps, B, F, Tn, N, wp, None, out, omap, mfma_only=True)
+        dw = torch.zeros_like(wp)
+        ops.conv_wgrad([ops.seg_bftc(x)], taps, B, F, Tn, N, dy, omap, dw)
+        torch.cuda.synchronize()
+        return out, dw
+
+    first = launch()
+    (plan,) = ops._CONV_PLANS.values()
+    (wplan,) = ops._WGRAD_PLANS.values()
+    for desc, (kt, ks) in ((plan.desc, plan.ktab), (wplan[0], wplan[3])):
+        assert (desc.ktab, desc.kseg) == (kt.data_ptr(), ks.data_ptr())
+    ops._ktab.cache_clear()  # what the 1025th signature does to the oldest table
+    gc.collect()
+    torch.cuda.empty_cache()
+    junk = [torch.full((256,), -1, dtype=torch.int32, device=DEV) for _ in range(64)]
+    again = launch()
+    assert len(ops._CONV_PLANS) == 1 and len(ops._WGRAD_PLANS) == 1 and junk
+    assert torch.equal(again[0], first[0]) and torch.equal(again[1], first[1])

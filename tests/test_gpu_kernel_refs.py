@@ -1,7 +1,9 @@
 """The small kernels of the training backward and the losses, each against the float64 references
 of tests/kernel_refs.py: the ReviewKD fusion backward with its folds and BatchNorm partials, the
 nearest down-sum, the framing pad / overlap-add / log-magnitude / complex-combine backwards with
-their forwards, SI-SNR, and the SPKD gradient pair spkd_grad + gram_bwd.
+their forwards, SI-SNR, the SPKD gradient pair spkd_grad + gram_bwd, and the BatchNorm forward
+kernels (statistics, finalize, eval coefficients, apply + PReLU) at channel counts that are no
+power of two.
 
 One tolerance rule for every floating-point comparison (kernel_refs.tolerance): with ref64 the
 float64 reference on exactly the kernel's inputs (bf16 inputs rounded first, float arguments as
@@ -396,3 +398,150 @@ def test_gram_bwd_views_accumulate_and_offsets(B):
                 r = torch.einsum("bk,kpc->bpc", M.to(dt), z.to(dt))
                 refs.append(r + prior.to(dt) if acc else r)
             _check(f"gram_bwd[{tag},B{B},acc{int(acc)}]", got, refs[0], refs[1])
+
+
+# ------------------------------------------------------------------------------------------
+# F. BatchNorm + PReLU at channel counts that are no power of two (csrc/norm.hip)
+# ------------------------------------------------------------------------------------------
+# The statistics kernel maps lanes to (row lane, channel quad): with C/4 not dividing 256 the last
+# lanes idle; the apply kernel keeps one group of 8 channels per lane only while C/8 divides its
+# grid stride.  16-bit storage: the reference is the float64 result on the rounded inputs, rounded
+# once to the storage type, and one ulp of that type is allowed on top of the rule.
+f16 = torch.float16
+EPS, MOM = 1e-5, 0.1
+
+
+def _ulp(ref, dtype):
+    """One unit in the last place of dtype at each |ref| (0 for float32: the rule alone)."""
+    if dtype == f32:
+        return torch.zeros_like(ref, dtype=f64)
+    _, e = torch.frexp(ref.to(dtype).double().abs().clamp(min=float(torch.finfo(dtype).tiny)))
+    return torch.ldexp(torch.full_like(ref, torch.finfo(dtype).eps, dtype=f64), e - 1)
+
+
+def _check_stored(case, got, ref64, ref32, dtype):
+    """got (stored as dtype) against ref64 rounded once to dtype: the rule plus one ulp."""
+    e32, tol = R.tolerance(ref64, ref32)
+    want = ref64.to(dtype).double()
+    err = (got.detach().double().cpu() - want).abs()
+    tol_t = tol + _ulp(want, dtype)
+    i = int(torch.argmax(err / tol_t))
+    print(f"KREF {case} e32={e32:.3e} err={err.reshape(-1)[i].item():.3e} "
+          f"tol={tol_t.reshape(-1)[i].item():.3e}")
+    assert torch.isfinite(err).all(), case
+    assert (err <= tol_t).all(), (case, e32, err.reshape(-1)[i].item(), tol_t.reshape(-1)[i].item())
+
+
+def _bn_case(rows, C, dt):
+    """Inputs as the kernel receives them (x rounded to its storage type) in float64 / float32."""
+    d = R.bn_inputs(rows, C)
+    d["x"] = d["x"].to(dt).float()
+    return d, {k: v.double() for k, v in d.items()}
+
+
+@pytest.mark.parametrize("dt", [f32, bf], ids=["fp32", "bf16"])
+@pytest.mark.parametrize("rows", R.BN_ROWS)
+@pytest.mark.parametrize("C", R.BN_CHANNELS)
+def test_batch_norm_train_against_fp64(C, rows, dt):
+    """ops.batch_norm_bftc(train=True): statistics, finalize, apply + PReLU, stats_out and one
+    running update.  rows = 1: the unbiased factor rows / (rows - 1) is undefined (torch refuses
+    the input); the kernel then updates running_var with the biased variance, 0 — finite — and
+    only the batch mean, the biased variance and y are compared beside that statement."""
+    from clskd import ops
+    d32, d64 = _bn_case(rows, C, dt)
+    alpha = torch.tensor([0.25])
+    args = lambda d: (d["x"], d["gamma"], d["beta"], d["rm"], d["rv"], EPS, MOM,  # noqa: E731
+                      alpha.to(d["x"].dtype))
+    r64, r32 = R.batch_norm_train(*args(d64)), R.batch_norm_train(*args(d32))
+    x = _dev(d32["x"].to(dt)).view(1, rows, 1, C)
+    y = torch.full_like(x, float("nan"))
+    rm, rv = _dev(d32["rm"].clone()), _dev(d32["rv"].clone())
+    mv = torch.full((2, C), float("nan"), device=DEV)
+    _, coef = ops.batch_norm_bftc(x, y, _dev(d32["gamma"]), _dev(d32["beta"]), rm, rv, True, MOM,
+                                  EPS, 1, alpha=_dev(alpha), stats_out=(mv[0], mv[1]),
+                                  return_coef=True)
+    torch.cuda.synchronize()
+    tag = f"bn_train C={C} rows={rows} {str(dt)[6:]}"
+    _check(f"{tag} mean", mv[0], r64["mean"], r32["mean"])
+    _check(f"{tag} var", mv[1], r64["var"], r32["var"])
+    if rows == 1:  # running_var <- (1 - momentum) running_var + momentum * 0: finite
+        assert torch.equal(mv[1].cpu(), torch.zeros(C)) and torch.isfinite(rv).all()
+    else:
+        _check(f"{tag} scale", coef[:C], r64["scale"], r32["scale"])
+        _check(f"{tag} shift", coef[C:], r64["shift"], r32["shift"])
+    _check(f"{tag} running_var", rv, r64["rv"], r32["rv"])
+    _check(f"{tag} running_mean", rm, r64["rm"], r32["rm"])
+    _check_stored(f"{tag} y", y.view(rows, C), r64["y"], r32["y"], dt)
+
+
+@pytest.mark.parametrize("dt", [f32, bf], ids=["fp32", "bf16"])
+@pytest.mark.parametrize("rows", R.BN_ROWS)
+@pytest.mark.parametrize("C", R.BN_CHANNELS)
+def test_batch_norm_eval_against_fp64(C, rows, dt):
+    """ops.batch_norm_bftc(train=False): clskd_bn_eval_coeffs + apply + PReLU; the running
+    statistics stay as they are."""
+    from clskd import ops
+    d32, d64 = _bn_case(rows, C, dt)
+    alpha = torch.tensor([0.25])
+    args = lambda d: (d["x"], d["gamma"], d["beta"], d["rm"], d["rv"], EPS,  # noqa: E731
+                      alpha.to(d["x"].dtype))
+    r64, r32 = R.batch_norm_eval(*args(d64)), R.batch_norm_eval(*args(d32))
+    x = _dev(d32["x"].to(dt)).view(1, rows, 1, C)
+    y = torch.full_like(x, float("nan"))
+    rm, rv = _dev(d32["rm"].clone()), _dev(d32["rv"].clone())
+    _, coef = ops.batch_norm_bftc(x, y, _dev(d32["gamma"]), _dev(d32["beta"]), rm, rv, False, MOM,
+                                  EPS, 1, alpha=_dev(alpha), return_coef=True)
+    torch.cuda.synchronize()
+    tag = f"bn_eval C={C} rows={rows} {str(dt)[6:]}"
+    assert torch.equal(rm.cpu(), d32["rm"]) and torch.equal(rv.cpu(), d32["rv"])
+    _check(f"{tag} scale", coef[:C], r64["scale"], r32["scale"])
+    _check(f"{tag} shift", coef[C:], r64["shift"], r32["shift"])
+    _check_stored(f"{tag} y", y.view(rows, C), r64["y"], r32["y"], dt)
+
+
+def _apply_case(rows, C, dt, slopes, inplace):
+    """ops.bn_apply (no slope / one slope) or clskd_bn_apply_reim (two) on given coefficients."""
+    from clskd import ops
+    d32, d64 = _bn_case(rows, C, dt)
+    al = [None if a is None else torch.tensor(a) for a in (list(slopes) + [None, None])[:2]]
+    ref = lambda d: R.bn_affine(d["x"], d["scale"], d["shift"],  # noqa: E731
+                                *[None if a is None else a.to(d["x"].dtype) for a in al])
+    r64, r32 = ref(d64), ref(d32)
+    x = _dev(d32["x"].to(dt)).view(1, rows, 1, C)
+    y = x if inplace else torch.full_like(x, float("nan"))
+    coef = _dev(torch.cat([d32["scale"], d32["shift"]]).contiguous())
+    if len(slopes) == 2:
+        alpha = _dev(torch.tensor(list(slopes)))
+        sc = coef.data_ptr()
+        ops.check(ops.lib().clskd_bn_apply_reim(x.data_ptr(), y.data_ptr(), rows, C, sc, sc + 4 * C,
+                                                alpha.data_ptr(), ops._dt(x), ops._stream()),
+                  "bn_apply_reim")
+    else:
+        out = ops.bn_apply(x, y, coef, _dev(torch.tensor([slopes[0]])) if slopes else None)
+        assert out is y
+    torch.cuda.synchronize()
+    _check_stored(f"bn_apply C={C} rows={rows} {str(dt)[6:]} slopes={slopes}"
+                  + (" in place" if inplace else ""), y.view(rows, C), r64, r32, dt)
+
+
+@pytest.mark.parametrize("dt", [f32, bf, f16], ids=["fp32", "bf16", "fp16"])
+@pytest.mark.parametrize("slopes", [(), (0.25,), (0.25, 0.05)], ids=["affine", "prelu", "reim"])
+@pytest.mark.parametrize("rows", R.BN_ROWS)
+@pytest.mark.parametrize("C", R.BN_CHANNELS)
+def test_bn_apply_against_fp64(C, rows, slopes, dt):
+    _apply_case(rows, C, dt, slopes, inplace=False)
+
+
+@pytest.mark.parametrize("slopes", [(0.25,), (0.25, 0.05)], ids=["prelu", "reim"])
+@pytest.mark.parametrize("C", R.BN_CHANNELS)
+def test_bn_apply_in_place(C, slopes):
+    _apply_case(4864, C, f32, slopes, inplace=True)
+
+
+@pytest.mark.parametrize("slopes", [(0.25,), (0.25, 0.05)], ids=["prelu", "reim"])
+def test_bn_apply_lanes_that_change_channel_group(slopes):
+    """More items than the largest grid (4096 x 256) at C/8 = 3: the lanes that visit a second
+    item find it in another channel group and reload their coefficients."""
+    rows, C = R.BN_APPLY_LARGE
+    assert rows * C // 8 > 4096 * 256 and (4096 * 256) % (C // 8) != 0
+    _apply_case(rows, C, f32, slopes, inplace=False)

@@ -218,3 +218,33 @@ def test_spkd_matrix_against_finite_differences(B, batchmean):
         (dG,) = torch.autograd.grad(R.spkd_from_grams(G, Gt, batchmean, 0.37), G)
         assert abs(fd - dG[i, j].item()) <= 1e-6 * dG.abs().max().item() + 1e-18, (i, j)
         torch.testing.assert_close(M, dG + dG.t(), rtol=1e-12, atol=1e-20)
+
+
+def test_batch_norm_references_against_torch():
+    """kernel_refs.batch_norm_train / batch_norm_eval / bn_affine against F.batch_norm + F.prelu
+    (float64), the two-slope PReLU against a per-channel loop, and the one-row statement."""
+    import torch.nn.functional as F
+    for rows, C in ((37, 24), (4864, 200)):
+        d = {k: v.double() for k, v in R.bn_inputs(rows, C).items()}
+        a = torch.tensor([0.25], dtype=torch.float64)
+        r = R.batch_norm_train(d["x"], d["gamma"], d["beta"], d["rm"], d["rv"], 1e-5, 0.1, a)
+        rm, rv = d["rm"].clone(), d["rv"].clone()
+        y = F.prelu(F.batch_norm(d["x"], rm, rv, d["gamma"], d["beta"], True, 0.1, 1e-5), a)
+        assert (r["y"] - y).abs().max() < 1e-12
+        assert (r["rm"] - rm).abs().max() < 1e-12 and (r["rv"] - rv).abs().max() < 1e-12
+        assert (r["var"] - d["x"].var(0, unbiased=False)).abs().max() < 1e-12
+        e = R.batch_norm_eval(d["x"], d["gamma"], d["beta"], d["rm"], d["rv"], 1e-5, a)
+        ye = F.prelu(F.batch_norm(d["x"], d["rm"], d["rv"], d["gamma"], d["beta"], False, 0.1, 1e-5), a)
+        assert (e["y"] - ye).abs().max() < 1e-12
+        two = R.bn_affine(d["x"], d["scale"], d["shift"], 0.25, 0.05)
+        lin = d["x"] * d["scale"] + d["shift"]
+        for c in range(C):
+            slope = 0.25 if c < C // 2 else 0.05
+            assert torch.equal(two[:, c], torch.where(lin[:, c] >= 0, lin[:, c], slope * lin[:, c]))
+        assert (two < 0).any() and (two > 0).any()
+    d = {k: v.double() for k, v in R.bn_inputs(1, 8).items()}
+    r = R.batch_norm_train(d["x"], d["gamma"], d["beta"], d["rm"], d["rv"], 1e-5, 0.1)
+    assert torch.equal(r["var"], torch.zeros(8, dtype=torch.float64))
+    assert torch.equal(r["rv"], 0.9 * d["rv"]) and torch.isfinite(r["y"]).all()
+    rows, C = R.BN_APPLY_LARGE
+    assert rows * C // 8 > 4096 * 256 and (4096 * 256) % (C // 8)
