@@ -220,6 +220,56 @@ __device__ __forceinline__ int xcd_tile(int bid, int nb) {
   return x * q + (x < r ? x : r) + j;
 }
 
+// ---- clskd_conv_desc's output map, and small helpers more than one conv kernel family uses ----
+// element offset of output row (b, fo, to): of_mul / of_add interleave the polyphase decoder rows
+__host__ __device__ __forceinline__ int64_t conv_out_row(const clskd_conv_desc& d, int64_t b, int fo, int to) {
+  return b * d.oB + (int64_t)(fo * d.of_mul + d.of_add) * d.oF + (int64_t)to * d.oT;
+}
+// element offset of output column n (split column map: n = hi * nlo + lo)
+__host__ __device__ __forceinline__ int64_t conv_col_off(const clskd_conv_desc& d, int n) {
+  return (int64_t)(n / d.nlo) * d.oNhi + (int64_t)(n % d.nlo) * d.oNlo;
+}
+// row inside a 32x32 MFMA accumulator of element r (0..15) held by lane half h
+__host__ __device__ constexpr int acc_row(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
+
+// select the per-segment value without runtime-indexed arrays (which would go to scratch): two
+// levels of value selects (v_cndmask); an if-else chain compiles to exec-mask branches
+template <typename T>
+__device__ __forceinline__ T sel4(int s, T a0, T a1, T a2, T a3) {
+  const T lo = (s & 1) ? a1 : a0;
+  const T hi = (s & 1) ? a3 : a2;
+  return (s & 2) ? hi : lo;
+}
+
+// the if-else chain form: conv_bf16.hip and conv_direct.hip lose occupancy with the select tree
+template <typename T>
+__device__ __forceinline__ T sel4_chain(int s, T a0, T a1, T a2, T a3) {
+  return s == 0 ? a0 : (s == 1 ? a1 : (s == 2 ? a2 : a3));
+}
+
+template <typename OutT>
+__device__ __forceinline__ void store_out(OutT* p, float v) { *p = (OutT)v; }
+
+// vmcnt takes immediates only: wait until at most n of this wave's VMEM ops are outstanding
+template <int MAXN>
+__device__ __forceinline__ void wait_vm(int n) {
+  if constexpr (MAXN <= 0) {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  } else {
+    if (n >= MAXN) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(MAXN) : "memory");
+    else wait_vm<MAXN - 1>(n);
+  }
+}
+
+// raw workgroup barrier that leaves LDS-DMA in flight: this wave's LDS reads/writes retired
+// first (lgkmcnt), then s_barrier; the compiler may not move memory operations across it
+__device__ __forceinline__ void raw_barrier() {
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  __builtin_amdgcn_sched_barrier(0);
+  __builtin_amdgcn_s_barrier();
+  __builtin_amdgcn_sched_barrier(0);
+}
+
 __device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
 
 // LSTM gate nonlinearities on v_exp_f32 / v_rcp_f32 (~1 ulp each; the recurrence's fp32 rounding,

@@ -16,14 +16,13 @@
 #include <stdlib.h>
 
 #include "conv_dispatch.h"
+#include "conv_gemm_common.h"
 
 namespace clskd {
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __attribute__((address_space(3))) void lds_void_t;
 typedef __attribute__((address_space(1))) void glb_void_t;
-
-__device__ __attribute__((aligned(64))) unsigned char g_zero_page[64];
 
 namespace v2 {
 // Tile geometry: BM output rows x BK reduction columns per stage; LDS rows of BK bf16
@@ -36,18 +35,6 @@ __device__ __forceinline__ int swz(int row) {
   if constexpr (BK == 64) return (row >> 1) & 7;
   else return (row >> 2) & 3;
 }
-
-template <typename T>
-__device__ __forceinline__ T sel4(int s, T a0, T a1, T a2, T a3) {
-  return s == 0 ? a0 : (s == 1 ? a1 : (s == 2 ? a2 : a3));
-}
-
-template <typename OutT>
-__device__ __forceinline__ void store_out(OutT* p, float v);
-template <>
-__device__ __forceinline__ void store_out<float>(float* p, float v) { *p = v; }
-template <>
-__device__ __forceinline__ void store_out<__bf16>(__bf16* p, float v) { *p = (__bf16)v; }
 
 __host__ __device__ constexpr int stage_bytes(int BM, int BK, int BN) { return (BM + BN) * BK * 2; }
 
@@ -113,7 +100,7 @@ __global__ __launch_bounds__(NW * 64) void conv_igemm_bf16_dma(const ConvArgsV2 
   const int nk = d.K / BK;
   const int64_t FoTo = (int64_t)d.Fo * d.To;
 
-  // ---- per-block tables -------------------------------------------------------------------
+  // ---- per-block tables (own row entry; statistics and scalar stores below too: DESIGN.md §26) --
   if (tid < BM) {
     const int64_t m = m0 + tid;
     const bool valid = m < M;
@@ -136,19 +123,14 @@ __global__ __launch_bounds__(NW * 64) void conv_igemm_bf16_dma(const ConvArgsV2 
     const uint64_t pv = (uint64_t)(uintptr_t)g.ptr;
     segtab[tid] = make_int4((int)(unsigned)pv, (int)(unsigned)(pv >> 32), g.F, g.T);
   }
-  for (int q = tid; q < d.K / 8; q += NT) {
-    const clskd_ktab_entry e = d.ktab[q * 8];
-    const int s = d.kseg[q * 8];
-    ctab[q] = make_int2(e.off, (int)(((unsigned)e.dF & 0xFFFFu) | (((unsigned)e.dT & 0xFFu) << 16) |
-                                     ((unsigned)s << 24)));
-  }
+  gemm_ctab_fill<8>(ctab, d, tid, NT);
   __syncthreads();
 
   const unsigned short* wgt = reinterpret_cast<const unsigned short*>(d.weight);
   const int prow = lane / CPR;  // row within an RPD-row DMA group
   const int ppos = lane % CPR;  // 16-B chunk position within the LDS row
 
-  const uint64_t zero_addr = (uint64_t)(uintptr_t)g_zero_page;
+  const uint64_t zero_addr = (uint64_t)(uintptr_t)gemm_zero_page;
   const unsigned stage_lds0 = __builtin_amdgcn_readfirstlane(lds_addr(stages));
   // Loop-invariant geometry of this lane's A rows (one per DMA group i): the per-K-tile source
   // address then costs ONE LDS read (the K-chunk entry) plus ALU — the issue step is no longer
@@ -175,18 +157,17 @@ __global__ __launch_bounds__(NW * 64) void conv_igemm_bf16_dma(const ConvArgsV2 
     uint64_t srcA[NGA], srcB[NGB];
 #pragma unroll
     for (int i = 0; i < NGA; ++i) {
-      const int2 ce = ctab[kt * CPR + a_c[i]];
-      const int sg = (int)((unsigned)ce.y >> 24);
-      const int dF = (int)(short)(ce.y & 0xFFFF);
-      const int dT = (int)(signed char)((ce.y >> 16) & 0xFF);
+      const KChunk ce = kchunk_decode(ctab[kt * CPR + a_c[i]]);
+      const int sg = ce.seg, dF = ce.dF, dT = ce.dT;
       const int fi = a_fi0[i] + dF;
       const int ti = a_ti0[i] + dT;
-      const int Fb = sel4(sg, d.seg[0].F, d.seg[1].F, d.seg[2].F, d.seg[3].F);
-      const int Tb = sel4(sg, d.seg[0].T, d.seg[1].T, d.seg[2].T, d.seg[3].T);
+      // (the chain form: with the select tree of sel4 twelve instances lose an occupancy step)
+      const int Fb = sel4_chain(sg, d.seg[0].F, d.seg[1].F, d.seg[2].F, d.seg[3].F);
+      const int Tb = sel4_chain(sg, d.seg[0].T, d.seg[1].T, d.seg[2].T, d.seg[3].T);
       const bool ok = a_valid[i] && (unsigned)fi < (unsigned)Fb && (unsigned)ti < (unsigned)Tb;
-      const uint64_t base = sel4(sg, sp0, sp1, sp2, sp3);
-      const int rb = sel4(sg, a_rb[i][0], a_rb[i][1], a_rb[i][2], a_rb[i][3]);
-      const int64_t eoff = (int64_t)rb + ce.x;
+      const uint64_t base = sel4_chain(sg, sp0, sp1, sp2, sp3);
+      const int rb = sel4_chain(sg, a_rb[i][0], a_rb[i][1], a_rb[i][2], a_rb[i][3]);
+      const int64_t eoff = (int64_t)rb + ce.off;
       srcA[i] = ok ? base + (uint64_t)(eoff * 2) : zero_addr;
     }
 #pragma unroll
@@ -299,7 +280,7 @@ __global__ __launch_bounds__(NW * 64) void conv_igemm_bf16_dma(const ConvArgsV2 
       for (int i = 0; i < TM; ++i)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const int row = wm * (BM / WM) + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+          const int row = wm * (BM / WM) + i * 32 + acc_row(r, h);
           if (out_row[row] >= 0) {
             const float v = acc[i][j][r];
             sm += v;
@@ -352,7 +333,7 @@ __global__ __launch_bounds__(NW * 64) void conv_igemm_bf16_dma(const ConvArgsV2 
       for (int i = 0; i < TM; ++i)
 #pragma unroll
         for (int r = 0; r < 16; ++r)
-          wt[(i * 32 + (r & 3) + 8 * (r >> 2) + 4 * h) * WC + j * 32 + l32] = (OutT)acc[i][j][r];
+          wt[(i * 32 + acc_row(r, h)) * WC + j * 32 + l32] = (OutT)acc[i][j][r];
     constexpr int CPRW = WC / CH;  // 16-B chunks per sub-tile row
 #pragma unroll
     for (int q0 = 0; q0 < WR * CPRW; q0 += 64) {
@@ -377,12 +358,12 @@ __global__ __launch_bounds__(NW * 64) void conv_igemm_bf16_dma(const ConvArgsV2 
   for (int j = 0; j < TN; ++j) {
     const int n = n0 + wn * (BN / WN) + j * 32 + l32;
     if (n >= d.N) continue;
-    const int64_t coff = (int64_t)(n / d.nlo) * d.oNhi + (int64_t)(n % d.nlo) * d.oNlo;
+    const int64_t coff = conv_col_off(d, n);
 #pragma unroll
     for (int i = 0; i < TM; ++i) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int row = wm * (BM / WM) + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+        const int row = wm * (BM / WM) + i * 32 + acc_row(r, h);
         const int64_t ro = out_row[row];
         if (DBG != 3 && ro >= 0) {
           float v = acc[i][j][r];

@@ -23,11 +23,6 @@ struct DirectArgs {
 typedef __bf16 bf16x8d __attribute__((ext_vector_type(8)));
 typedef float f32x2d __attribute__((ext_vector_type(2)));
 
-template <typename T>
-__device__ __forceinline__ T sel4d(int s, T a0, T a1, T a2, T a3) {
-  return s == 0 ? a0 : (s == 1 ? a1 : (s == 2 ? a2 : a3));
-}
-
 template <typename OutT, int VW>
 struct VecOf;
 template <> struct VecOf<float, 4> { typedef f32x4 T; };
@@ -88,8 +83,8 @@ __global__ __launch_bounds__(128) void conv_direct_kernel(const DirectArgs args)
   for (int j = tid; j < nrun; j += 128) {
     const clskd_ktab_entry e = d.ktab[j * G];
     const int sg = d.kseg[j * G];
-    const int FT = (int)(uint16_t)sel4d(sg, d.seg[0].F, d.seg[1].F, d.seg[2].F, d.seg[3].F) |
-                   (sel4d(sg, d.seg[0].T, d.seg[1].T, d.seg[2].T, d.seg[3].T) << 16);
+    const int FT = (int)(uint16_t)sel4_chain(sg, d.seg[0].F, d.seg[1].F, d.seg[2].F, d.seg[3].F) |
+                   (sel4_chain(sg, d.seg[0].T, d.seg[1].T, d.seg[2].T, d.seg[3].T) << 16);
     kl[j] = make_int4(e.off, (int)(uint16_t)e.dF | ((int)e.dT << 16), sg, FT);
   }
   __syncthreads();
@@ -240,7 +235,7 @@ __global__ __launch_bounds__(128) void conv_direct_kernel(const DirectArgs args)
 
   if (!valid) return;
   OutT* outp = reinterpret_cast<OutT*>(d.out);
-  const int64_t ro = (int64_t)b * d.oB + (int64_t)(fo * d.of_mul + d.of_add) * d.oF + (int64_t)to * d.oT;
+  const int64_t ro = conv_out_row(d, b, fo, to);
   constexpr int VWMAX = 16 / sizeof(OutT);
   constexpr int VW = NP < VWMAX ? NP : VWMAX;
   const bool vec = d.N == NP && d.oNlo == 1 && d.nlo >= NP && d.oB % VW == 0 && d.oF % VW == 0 &&
@@ -265,7 +260,7 @@ __global__ __launch_bounds__(128) void conv_direct_kernel(const DirectArgs args)
     for (int n = 0; n < NP; ++n) {
       if (n < d.N) {
         const int64_t o = ro + (d.nlo >= NP ? (int64_t)n * d.oNlo
-                                            : (int64_t)(n / d.nlo) * d.oNhi + (int64_t)(n % d.nlo) * d.oNlo);
+                                            : conv_col_off(d, n));
         outp[o] = (OutT)(d.accumulate ? acc[n] + (float)outp[o] : acc[n]);
       }
     }

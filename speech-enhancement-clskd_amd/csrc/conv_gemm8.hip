@@ -34,14 +34,13 @@
 
 #include "bnfold.h"
 #include "conv_dispatch.h"
+#include "conv_gemm_common.h"
 
 namespace clskd {
 
 typedef short bf16x8s __attribute__((ext_vector_type(8)));
 
 namespace g8 {
-
-__device__ __attribute__((aligned(64))) unsigned char zero_page[64];
 
 // Tap-addressed pieces (TA): the buffer form of the LDS-DMA, four 1-KiB pieces per call.  Lane l
 // copies 16 B from rsrc.base + voff[l] to m0 + 16*l (out-of-range offsets, >= num_records = 2^31,
@@ -98,31 +97,6 @@ __device__ __forceinline__ void bdma2(unsigned v0, unsigned v1, i32x4 rs, unsign
       : "=&s"(keep)
       : "s"(lds_base), "s"(rs), "v"(v0), "v"(v1), "n"(O0), "n"(O0 + OS)
       : "memory");
-}
-
-template <typename T>
-__device__ __forceinline__ T sel4(int s, T a0, T a1, T a2, T a3) {
-  return s == 0 ? a0 : (s == 1 ? a1 : (s == 2 ? a2 : a3));
-}
-
-// raw workgroup barrier that leaves LDS-DMA in flight: this wave's LDS reads/writes retired
-// first (lgkmcnt), then s_barrier; the compiler may not move memory operations across it
-__device__ __forceinline__ void raw_barrier() {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_sched_barrier(0);
-  __builtin_amdgcn_s_barrier();
-  __builtin_amdgcn_sched_barrier(0);
-}
-
-// vmcnt takes immediates only: wait until at most n of this wave's VMEM ops are outstanding
-template <int MAXN>
-__device__ __forceinline__ void wait_vm(int n) {
-  if constexpr (MAXN <= 0) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  } else {
-    if (n >= MAXN) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(MAXN) : "memory");
-    else wait_vm<MAXN - 1>(n);
-  }
 }
 
 // Row table of one tile (double-buffered in LDS).
@@ -221,7 +195,8 @@ __global__ __launch_bounds__(NWV * 64) void conv_gemm8_kernel(const ConvArgsG8 a
   const int nk = d.K / BK;
   const int64_t FoTo = (int64_t)d.Fo * d.To;
 
-  // ---- this workgroup's tile list (XCD-aware contiguous runs) ------------------------------
+  // ---- this workgroup's tile list (XCD-aware contiguous runs; own copy, as the row table below:
+  //      shared forms spill SGPRs in the stream-K instances) ----------------------
   const int grid = gridDim.x, b = blockIdx.x;
   int t_first = 0, t_step = 1, ntl;
   const bool sk = (TA & 2) != 0 && PP == 0 && args.sk_cnt != nullptr;  // compile-time off unless TA bit 1
@@ -310,12 +285,7 @@ __global__ __launch_bounds__(NWV * 64) void conv_gemm8_kernel(const ConvArgsG8 a
       kinfo[q] = make_int4((int)(uint32_t)a, (int)(uint32_t)(a >> 32), t * d.nseg + s, s);
     }
   } else {
-    for (int q = tid; q < d.K / 8; q += NT) {
-      const clskd_ktab_entry e = d.ktab[q * 8];
-      const int s = d.kseg[q * 8];
-      ctab[q] = make_int2(e.off, (int)(((unsigned)e.dF & 0xFFFFu) | (((unsigned)e.dT & 0xFFu) << 16) |
-                                       ((unsigned)s << 24)));
-    }
+    gemm_ctab_fill<8>(ctab, d, tid, NT);
   }
   for (int n = tid; n < d.N; n += NT) bias_l[n] = d.bias ? d.bias[n] : 0.f;
   build_table(0, 0);
@@ -367,18 +337,19 @@ __global__ __launch_bounds__(NWV * 64) void conv_gemm8_kernel(const ConvArgsG8 a
     geo_tile = j;
   };
 
-  const uint64_t zero_addr = (uint64_t)(uintptr_t)g8::zero_page;
+  const uint64_t zero_addr = (uint64_t)(uintptr_t)gemm_zero_page;
   const unsigned stage_lds0 = __builtin_amdgcn_readfirstlane(lds_addr(stages));
   const uint64_t sp0 = (uint64_t)(uintptr_t)d.seg[0].ptr, sp1 = (uint64_t)(uintptr_t)d.seg[1].ptr;
   struct KEnt {
     int off, dF, dT, Fb, Tb, s1;
   };
   auto kdecode = [&](int2 ce) -> KEnt {
+    const KChunk c = kchunk_decode(ce);
     KEnt e;
-    e.s1 = (int)((unsigned)ce.y >> 24);
-    e.off = ce.x;
-    e.dF = (int)(short)(ce.y & 0xFFFF);
-    e.dT = (int)(signed char)((ce.y >> 16) & 0xFF);
+    e.s1 = c.seg;
+    e.off = c.off;
+    e.dF = c.dF;
+    e.dT = c.dT;
     e.Fb = e.s1 ? d.seg[1].F : d.seg[0].F;
     e.Tb = e.s1 ? d.seg[1].T : d.seg[0].T;
     return e;
@@ -540,7 +511,7 @@ __global__ __launch_bounds__(NWV * 64) void conv_gemm8_kernel(const ConvArgsG8 a
     for (int w = 0; w < NS - 1; ++w)
       if (w < total) issue_all(w);
   }
-  g8::wait_vm<(NS - 2) * G>(min(NS - 2, total - 1) * G);
+  wait_vm<(NS - 2) * G>(min(NS - 2, total - 1) * G);
   raw_barrier();
 
   constexpr int NSET = PF + 1;
@@ -641,7 +612,7 @@ __global__ __launch_bounds__(NWV * 64) void conv_gemm8_kernel(const ConvArgsG8 a
         } else if ((DBG >= 4 && DBG <= 5) || gk + 1 >= total) {
           asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         } else {
-          g8::wait_vm<(NS - 2) * G>(min(NS - 2, total - 2 - gk) * G);
+          wait_vm<(NS - 2) * G>(min(NS - 2, total - 2 - gk) * G);
         }
         raw_barrier();
         if (kt + 1 < nkj) read_head(stages + ((gk + 1) % NS) * SB);
@@ -772,7 +743,7 @@ __global__ __launch_bounds__(NWV * 64) void conv_gemm8_kernel(const ConvArgsG8 a
           for (int i = 0; i < FM; ++i)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-              const float v = (i * 32 + (r & 3) + 8 * (r >> 2)) < lim ? acc[i][jj][r] : 0.f;
+              const float v = (i * 32 + acc_row(r, 0)) < lim ? acc[i][jj][r] : 0.f;
               sm += v;
               sq = fmaf(v, v, sq);
             }
@@ -832,7 +803,7 @@ __global__ __launch_bounds__(NWV * 64) void conv_gemm8_kernel(const ConvArgsG8 a
 #pragma unroll
         for (int jj = 0; jj < FN; ++jj) {
 #pragma unroll
-          for (int r = 0; r < 16; ++r) wt[((r & 3) + 8 * (r >> 2) + 4 * h) * 32 + l32] = (OutT)acc[i][jj][r];
+          for (int r = 0; r < 16; ++r) wt[(acc_row(r, h)) * 32 + l32] = (OutT)acc[i][jj][r];
           asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // wave-local: tile written
 #pragma unroll
           for (int q0 = 0; q0 < 32 * CPRW; q0 += 64) {
@@ -850,12 +821,12 @@ __global__ __launch_bounds__(NWV * 64) void conv_gemm8_kernel(const ConvArgsG8 a
       for (int jj = 0; jj < FN; ++jj) {
         const int n = n0 + wn * WC + jj * 32 + l32;
         if (n >= d.N) continue;
-        const int64_t coff = (int64_t)(n / d.nlo) * d.oNhi + (int64_t)(n % d.nlo) * d.oNlo;
+        const int64_t coff = conv_col_off(d, n);
 #pragma unroll
         for (int i = 0; i < FM; ++i)
 #pragma unroll
           for (int r = 0; r < 16; ++r) {
-            const int row = wm * WR + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+            const int row = wm * WR + i * 32 + acc_row(r, h);
             const int64_t ro = tb.orow[row];
             if (ro >= 0) out[ro + coff] = (OutT)acc[i][jj][r];
           }

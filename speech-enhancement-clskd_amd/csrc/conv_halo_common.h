@@ -205,10 +205,6 @@ __device__ __forceinline__ void halo_stats_zero_unowned(double* stats, int N, in
     for (int i = threadIdx.x; i < N * 2; i += HALO_NTH) stats[s * stats_ld * 2 + i] = 0.0;
 }
 
-// output element offset of column n (-1 past N is the caller's)
-__device__ __forceinline__ int64_t halo_col_off(const clskd_conv_desc& d, int n) {
-  return (int64_t)(n / d.nlo) * d.oNhi + (int64_t)(n % d.nlo) * d.oNlo;
-}
 // bias and output offset of this lane's column in each of NB 32-column blocks: launch columns
 // [n0, n0 + N) of the descriptor's
 template <int NB, bool LAUNDER>
@@ -218,7 +214,7 @@ __device__ __forceinline__ void halo_bias_coff(const clskd_conv_desc& d, int n0,
   for (int nb = 0; nb < NB; ++nb) {
     const int n = nb * 32 + l32;
     bcol[nb] = (d.bias && n < N) ? d.bias[n0 + n] : 0.f;
-    const int64_t c = n < N ? halo_col_off(d, n0 + n) : -1;
+    const int64_t c = n < N ? conv_col_off(d, n0 + n) : -1;
     coff[nb] = LAUNDER ? vconst64(c) : c;
   }
 }

@@ -48,25 +48,6 @@ typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ int swz(int r) { return (r >> 2) & 3; }  // 64-B rows, 16-B chunks
 
-// vmcnt takes immediates only: wait until at most n of this wave's VMEM ops are outstanding
-template <int MAXN>
-__device__ __forceinline__ void wait_vm(int n) {
-  if constexpr (MAXN <= 0) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  } else {
-    if (n >= MAXN) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(MAXN) : "memory");
-    else wait_vm<MAXN - 1>(n);
-  }
-}
-
-// barrier that leaves LDS-DMA in flight (this wave's LDS reads retired first)
-__device__ __forceinline__ void raw_barrier() {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_sched_barrier(0);
-  __builtin_amdgcn_s_barrier();
-  __builtin_amdgcn_sched_barrier(0);
-}
-
 }  // namespace hw
 
 struct HwArgs {
@@ -151,7 +132,7 @@ __global__ __launch_bounds__(512) void conv_halow_kernel(const HwArgs a) {
   }
   for (int n = tid; n < BN; n += 512) {
     bias_l[n] = (d.bias && n < d.N) ? d.bias[n] : 0.f;
-    coff_l[n] = n < d.N ? halo_col_off(d, n) : -1;
+    coff_l[n] = n < d.N ? conv_col_off(d, n) : -1;
   }
   if (d.stats) {  // partial slots past the grid are zero (the slot contract of include/clskd.h)
     for (int64_t s = (int64_t)blockIdx.x + gridDim.x; s < g.nblk128; s += gridDim.x)
@@ -249,7 +230,7 @@ __global__ __launch_bounds__(512) void conv_halow_kernel(const HwArgs a) {
     issue_next_halo();   // chunk 0
     issue_next_slab();   // step 0
     issue_next_slab();   // step 1
-    hw::wait_vm<MAXG + 2 * GB>(total > 1 ? GB : 0);  // halo 0 and slab 0 landed
+    wait_vm<MAXG + 2 * GB>(total > 1 ? GB : 0);  // halo 0 and slab 0 landed
   }
   raw_barrier();
 
@@ -303,7 +284,7 @@ __global__ __launch_bounds__(512) void conv_halow_kernel(const HwArgs a) {
       mfma_k16(1);
       // the next step's slab (issued one step ago) and, at a chunk's last tap, the next
       // chunk's halo (issued at its first tap) have landed; younger pieces stay in flight
-      hw::wait_vm<MAXG + GB>(ib + ih + (t == 1 ? hprev : 0));
+      wait_vm<MAXG + GB>(ib + ih + (t == 1 ? hprev : 0));
       hprev = ih;
       raw_barrier();
       if (++t == NTAPS) {

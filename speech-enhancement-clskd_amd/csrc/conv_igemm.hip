@@ -14,6 +14,7 @@
 #include <stdlib.h>
 
 #include "conv_dispatch.h"
+#include "conv_gemm_common.h"
 
 namespace clskd {
 
@@ -27,18 +28,6 @@ struct ConvArgs {
 };
 
 __device__ __forceinline__ int swz(int row, int chunk) { return chunk ^ ((row >> 2) & 3); }
-
-// select the per-segment value without runtime-indexed arrays (which would go to scratch)
-template <typename T>
-__device__ __forceinline__ T sel4(int s, T a0, T a1, T a2, T a3) {
-  // two levels of value selects (v_cndmask): an if-else chain compiles to exec-mask branches
-  const T lo = (s & 1) ? a1 : a0;
-  const T hi = (s & 1) ? a3 : a2;
-  return (s & 2) ? hi : lo;
-}
-
-template <typename OutT>
-__device__ __forceinline__ void store_val(OutT* p, float v) { *p = (OutT)v; }
 
 template <int BN, bool VEC4, typename OutT, int NW = 4>
 __global__ __launch_bounds__(NW * 64) void conv_igemm_f32(const ConvArgs args) {
@@ -135,10 +124,8 @@ __global__ __launch_bounds__(NW * 64) void conv_igemm_f32(const ConvArgs args) {
 
   auto load_a = [&](int kt, f32x4 (&ra)[2]) {
     if constexpr (VEC4) {
-      const int2 ce = ctab[kt * (BK / 4) + kq];
-      const int sg = (int)((unsigned)ce.y >> 24);
-      const int dF = (int)(short)(ce.y & 0xFFFF);
-      const int dT = (int)(signed char)((ce.y >> 16) & 0xFF);
+      const KChunk ce = kchunk_decode(ctab[kt * (BK / 4) + kq]);
+      const int sg = ce.seg, dF = ce.dF, dT = ce.dT;
       const float* sp = sel4(sg, sp0, sp1, sp2, sp3);
       const int Fb = sel4(sg, d.seg[0].F, d.seg[1].F, d.seg[2].F, d.seg[3].F);
       const int Tb = sel4(sg, d.seg[0].T, d.seg[1].T, d.seg[2].T, d.seg[3].T);
@@ -149,7 +136,7 @@ __global__ __launch_bounds__(NW * 64) void conv_igemm_f32(const ConvArgs args) {
         const int rbase = sel4(sg, a_rb[i][0], a_rb[i][1], a_rb[i][2], a_rb[i][3]);
         f32x4 v = {0.f, 0.f, 0.f, 0.f};
         if (rvalid[i] && (unsigned)fi < (unsigned)Fb && (unsigned)ti < (unsigned)Tb)
-          v = *reinterpret_cast<const f32x4*>(sp + (int64_t)(rbase + ce.x));
+          v = *reinterpret_cast<const f32x4*>(sp + (int64_t)(rbase + ce.off));
         ra[i] = v;
       }
     } else {
@@ -324,7 +311,7 @@ __global__ __launch_bounds__(NW * 64) void conv_igemm_f32(const ConvArgs args) {
         if constexpr (sizeof(OutT) == 4) {
           if (d.accumulate) v += outp[ro + coff];
         }
-        store_val<OutT>(outp + ro + coff, v);
+        store_out<OutT>(outp + ro + coff, v);
       }
     }
   }

@@ -30,6 +30,7 @@
 
 #include "bnfold.h"
 #include "conv_dispatch.h"
+#include "conv_gemm_common.h"
 
 namespace clskd {
 
@@ -41,13 +42,6 @@ typedef short s16x8 __attribute__((ext_vector_type(8)));
 template <int BK>
 __device__ __forceinline__ int swz(int row) {
   return BK == 16 ? (row >> 3) & 1 : BK == 32 ? (row >> 2) & 3 : (row >> 1) & 7;
-}
-
-template <typename T>
-__device__ __forceinline__ T sel4(int s, T a0, T a1, T a2, T a3) {
-  const T lo = (s & 1) ? a1 : a0;
-  const T hi = (s & 1) ? a3 : a2;
-  return (s & 2) ? hi : lo;
 }
 }  // namespace sp3
 
@@ -177,10 +171,8 @@ __global__ __launch_bounds__(NW * 64) void conv_split3_kernel(const SplitArgs ar
   const float* wgt = reinterpret_cast<const float*>(d.weight);
   f32x4 ra[NRA], rb[NBL], ra2[NRA], rb2[NBL];  // ra2 / rb2: the second set (PD = 2)
   auto load_kt = [&](int kt, f32x4 (&xa)[NRA], f32x4 (&xb)[NBL]) {
-    const int2 ce = ctab[kt * QR + kq];
-    const int sg = (int)((unsigned)ce.y >> 24);
-    const int dF = (int)(short)(ce.y & 0xFFFF);
-    const int dT = (int)(signed char)((ce.y >> 16) & 0xFF);
+    const KChunk ce = kchunk_decode(ctab[kt * QR + kq]);
+    const int sg = ce.seg, dF = ce.dF, dT = ce.dT;
     const float* sp = sel4(sg, sp0, sp1, sp2, sp3);
     const int Fb = sel4(sg, d.seg[0].F, d.seg[1].F, d.seg[2].F, d.seg[3].F);
     const int Tb = sel4(sg, d.seg[0].T, d.seg[1].T, d.seg[2].T, d.seg[3].T);
@@ -190,7 +182,7 @@ __global__ __launch_bounds__(NW * 64) void conv_split3_kernel(const SplitArgs ar
       const int rbs = sel4(sg, arb[i][0], arb[i][1], arb[i][2], arb[i][3]);
       f32x4 v = {0.f, 0.f, 0.f, 0.f};
       if (rvl[i] && (unsigned)fi < (unsigned)Fb && (unsigned)ti < (unsigned)Tb)
-        v = *reinterpret_cast<const f32x4*>(sp + (int64_t)(rbs + ce.x));
+        v = *reinterpret_cast<const f32x4*>(sp + (int64_t)(rbs + ce.off));
       xa[i] = v;
     }
 #pragma unroll

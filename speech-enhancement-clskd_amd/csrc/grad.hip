@@ -104,7 +104,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_f32(const WgradArgs a) {
       }
       av[qq] = v;
     }
-    const int64_t orow = b * d.oB + (fo * d.of_mul + d.of_add) * d.oF + to * d.oT;
+    const int64_t orow = conv_out_row(d, b, (int)fo, (int)to);
 #pragma unroll
     for (int qq = 0; qq < 2; ++qq) {
       const int nl = (q0 + 8 * qq) * 4;
@@ -116,7 +116,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_f32(const WgradArgs a) {
 #pragma unroll
           for (int j = 0; j < 4; ++j) {
             const int n = n0 + nl + j;
-            if (n < d.N) v[j] = a.dy[orow + (int64_t)(n / d.nlo) * d.oNhi + (int64_t)(n % d.nlo) * d.oNlo];
+            if (n < d.N) v[j] = a.dy[orow + conv_col_off(d, n)];
           }
         }
       }

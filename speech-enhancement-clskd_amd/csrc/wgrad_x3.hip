@@ -167,7 +167,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_x3(const WgradX3Args a) {
   for (int j = 0; j < 4; ++j) {
     const int n = nl + j;
     cval[j] = n < d.N;
-    coff[j] = cval[j] ? (int64_t)(n / d.nlo) * d.oNhi + (int64_t)(n % d.nlo) * d.oNlo : 0;
+    coff[j] = cval[j] ? conv_col_off(d, n) : 0;
   }
 
   auto gather = [&](unsigned rc, float (&xa)[8][4], float (&xd)[RPL][4]) {  // chunk rows rc .. rc + 31
@@ -221,16 +221,14 @@ __global__ __launch_bounds__(256) void conv_wgrad_x3(const WgradX3Args a) {
       const unsigned m0 = rc + RPL * dg;
       if (m0 < r_end) p.set(m0, FoTo, d.To);
       const bool fast = m0 + RPL - 1 < r_end && p.to + RPL - 1 < d.To;
-      const int64_t orow0 = (int64_t)p.b * d.oB + (int64_t)(p.fo * d.of_mul + d.of_add) * d.oF +
-                            (int64_t)p.to * d.oT;
+      const int64_t orow0 = conv_out_row(d, p.b, p.fo, p.to);
 #pragma unroll
       for (int rr = 0; rr < RPL; ++rr) {
         f32x4 v = {0.f, 0.f, 0.f, 0.f};
         const bool valid = m0 + rr < r_end;
         if (valid) {
           const int64_t orow = fast ? orow0 + rr * d.oT
-                                    : (int64_t)p.b * d.oB + (int64_t)(p.fo * d.of_mul + d.of_add) * d.oF +
-                                          (int64_t)p.to * d.oT;
+                                    : conv_out_row(d, p.b, p.fo, p.to);
           if (dvec4 && ((orow + nl) & 3) == 0) {
             v = *reinterpret_cast<const f32x4*>(a.dy + orow + nl);
           } else {

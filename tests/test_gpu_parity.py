@@ -1230,6 +1230,98 @@ def test_conv_gemm8_against_torch(case, lp, engine, loop="phased"):
 
 
 
+_T33 = [(kf - 1, kt - 1) for kf in range(3) for kt in range(3)]
+FRAME_CASES = {
+    # engine: (operand type, segment channels, N, taps, Fo (= Fi), To, knobs, split products, kernel)
+    "igemm_f32": ("fp32", (8, 12), 40, _T33, 5, 13, {"CLSKD_NO_HALO32": 1}, False, "conv_igemm_f32"),
+    # 18 taps: more than the halo kernel's plan holds, so the 16-bit layer reaches the LDS-DMA engine
+    "lds_dma": ("bf16", (8, 8), 40, [(kf - 3, kt - 1) for kf in range(6) for kt in range(3)], 5, 13, {},
+                False, "conv_igemm_bf16_dma"),
+    "split3": ("fp32", (8, 12), 40, _T33, 5, 13, {"CLSKD_HALO_SPLIT": 0}, True, "conv_split3_kernel"),
+    "gemm8": ("bf16", (64, 64), 72, _T33, 3, 43, {}, False, "conv_gemm8_kernel"),
+}
+
+
+# (conv_gemm8 takes no accumulating launch: the dispatch table's gate)
+@pytest.mark.parametrize("engine,accumulate", [(e, a) for e in sorted(FRAME_CASES) for a in (False, True)
+                                               if not (a and e == "gemm8")])
+def test_conv_gemm_frame_edges(engine, accumulate):
+    """The frame the four implicit-GEMM engines share (csrc/conv_gemm_common.h), at its edges, on
+    each engine: B = 2 and M = B Fo To = one full M-tile of the engine (128 rows; 256 for
+    conv_gemm8) + 2 rows (M is even with B = 2), so the first tile straddles the batch boundary,
+    the second holds two valid rows and the last 128-row statistics block is partial; N = one
+    32-column block + 8 (72 for conv_gemm8, which takes N > 64); two segments; 3x3 (6x3) taps that
+    read outside F and T on both sides; the polyphase output map of_mul = 2, of_add = 1 with a
+    split column map (nlo = N / 2, oNhi != nlo * oNlo) into a padded buffer whose every other
+    element must stay bitwise as it was; fused statistics, or accumulate = 1 into a prefilled fp32
+    output (the engines that take it).  Reference: fp64 on the same operands; tolerance: each
+    engine's own rule (1e-5 fp32, 1e-4 for 16-bit operands into fp32, the split bound of
+    test_gpu_split.py; statistics 1e-5 relative).
+    Not here, because other tests hold them: a persistent engine with fewer workgroups than
+    statistics slots or tiles — test_split_conv_prefetch_depth / test_split_conv_lds_stages
+    (CLSKD_SPLIT_GRID=1, NaN-prefilled statistics: unowned slots must read zero) and
+    test_conv_gemm8_stream_k (grid 40 / 64 under the tile count, both deals).  More workgroups than
+    tiles (the ntl == 0 ticket) cannot be launched: both host plans use grid <= ntiles."""
+    from clskd import _lib, ops
+    from test_gpu_split import _ref
+    lp, segc, N, taps, Fo, To, knobs, split, kernel = FRAME_CASES[engine]
+    g = torch.Generator().manual_seed(len(engine) * 11 + N + int(accumulate))
+    B, Cin = 2, sum(segc)
+    dt = torch.bfloat16 if lp == "bf16" else torch.float32
+    segs = [torch.randn(B, Fo, To, c, generator=g).to(dt) for c in segc]
+    K = len(taps) * Cin
+    wp = ops.pack_weight((torch.randn(N, len(taps), Cin, generator=g) * (0.5 / K ** 0.5)).to(DEV), K, lp)
+    wq = wp[:, :K].float().cpu().double().view(N, len(taps), Cin)
+    bias = torch.randn(N, generator=g)
+    ref = _ref(segs, taps, 1, Fo, To, wq, bias)
+    mag = _ref([s.abs() for s in segs], taps, 1, Fo, To, wq.abs(), bias.abs())
+    nlo, oNhi = N // 2, N // 2 + 3
+    W = 2 * oNhi + 2  # elements per (b, f, t) of the buffer: two column halves, each padded
+    prior = (torch.randn(B, 2 * Fo, To, W, generator=g) if accumulate
+             else torch.full((B, 2 * Fo, To, W), 12345.0)).to(DEV)
+    out = prior.clone()
+    nblk = ops.conv_mblocks(B, Fo, To)
+    st = None if accumulate else torch.full((nblk * N * 2,), float("nan"), device=DEV, dtype=torch.float64)
+    prev = {k: _lib.set_knob(k, v) for k, v in knobs.items()}
+    try:
+        with ops.split_products(split):
+            ops.conv([ops.seg_bftc(s.to(DEV)) for s in segs], taps, B, Fo, To, N, wp, bias.to(DEV), out,
+                     ops.OutMap(2 * Fo * To * W, To * W, W, oNhi=oNhi, oNlo=1, nlo=nlo, of_mul=2, of_add=1),
+                     stats=st, accumulate=accumulate, mfma_only=True)
+        kname = ops.conv_kernel_of_last_launch()
+    finally:
+        for k, v in prev.items():
+            _lib.set_knob(k, v)
+    assert kname.startswith(kernel), kname
+    cols = torch.cat([torch.arange(nlo), oNhi + torch.arange(N - nlo)])
+    o, pr = out.cpu(), prior.cpu()
+    got = (o[:, 1::2][..., cols].double() - (pr[:, 1::2][..., cols].double() if accumulate else 0.0))
+    err = (got - ref).abs()
+    if engine == "split3":
+        bound = 2e-5 * mag + 1e-7
+    else:
+        tol = 1e-4 if lp == "bf16" else 1e-5
+        bound = tol + tol * ref.abs()
+    worst = float((err / bound).max())
+    print(f"FRAME {engine} accumulate={int(accumulate)}: max err {float(err.max()):.2e}, worst err/bound {worst:.3f}")
+    assert worst <= 1.0
+    touched = torch.zeros(B, 2 * Fo, To, W, dtype=torch.bool)
+    touched[:, 1::2, :, :nlo] = True
+    touched[:, 1::2, :, oNhi:oNhi + N - nlo] = True
+    assert torch.equal(o[~touched], pr[~touched]), "an element outside the output map was written"
+    if st is not None:
+        stc = st.view(nblk, N, 2).cpu()
+        assert torch.isfinite(stc).all(), "every statistics slot must be written"
+        S, Q = stc[..., 0].sum(0), stc[..., 1].sum(0)
+        np.testing.assert_allclose(S.numpy(), ref.sum((0, 1, 2)).numpy(), rtol=1e-5,
+                                   atol=1e-5 * float(mag.sum((0, 1, 2)).max()))
+        np.testing.assert_allclose(Q.numpy(), (ref * ref).sum((0, 1, 2)).numpy(), rtol=5e-5)
+        if engine in ("igemm_f32", "lds_dma", "gemm8"):  # one slot per 128-row block, in row order
+            rows = ref.reshape(-1, N)
+            np.testing.assert_allclose(stc[-1, :, 0].numpy(), rows[128 * (nblk - 1):].sum(0).numpy(),
+                                       rtol=1e-5, atol=1e-5 * float(mag.reshape(-1, N)[128 * (nblk - 1):].sum(0).max()))
+
+
 @pytest.mark.parametrize("prio", [0, 1])
 @pytest.mark.parametrize("variant", ["1", "2", "4", "8", "h16", "h64", "h128"])
 def test_lstm_recurrence_against_torch(variant, prio):
